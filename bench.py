@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- device-resident AES-GCM seal+open throughput of the MI355X engine (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c4s|c5]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c4s|c5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets the workload up in HBM, runs W warm-up steps,
+times K steps, writes the last step's outputs if --dump-outputs is given, and prints the result line.  --full adds
+every other measurement and check to that line, each outside the timed steps: parity (every record opens back to its
+bytes, sampled records against lib/fusion.c's digests), per-kernel times and the clock they ran at, the roofline, key
+setup from traffic secrets, the host-resident paths, the plugin at ptlsbench's shape and the CPU baseline.
 
 --gpus N > 1 without a launcher starts N rank processes itself (torch.distributed.run on 127.0.0.1, before
 any GPU call); under a launcher WORLD_SIZE must equal N.  Ranks meet only over gloo (CPU): barriers and the timing
@@ -18,8 +24,12 @@ meet at the barriers and the max-over-ranks of the timed region.
 
 Rank 0 prints ONE JSON line.  value = whole-job GiB/s = sum over ranks of 2 * sum(L) per step / the slowest
 rank's time; per_rank lists every rank's own rate.
-Extra fields: roofline (seal kernel vs the 8 TB/s HBM peak), cpu_baseline (lib/fusion.c on this host's
+Extra fields with --full: roofline (seal kernel vs the 8 TB/s HBM peak), cpu_baseline (lib/fusion.c on this host's
 cores, oracle/_ref), parity (sampled records vs the golden digests of lib/fusion.c + full open check).
+
+--dump-outputs DIR writes what the last timed step handed its caller as float32 arrays (dump_outputs): sealed.npy,
+opened.npy and result.npy (with the suffix _rank<r> at N > 1).  The inputs are seeded, so two builds run with the same
+arguments can be compared file for file.
 """
 import argparse
 import hashlib
@@ -673,6 +683,73 @@ def node_e2e(args, cfg, devices):
         node.close()
 
 
+DUMP_SEED = 0x64756D70
+DUMP_SEALED_BYTES = 8_000_000  # x 4 as float32; with opened and result the files stay under 64 MB
+DUMP_OPENED_BYTES = 4_000_000
+DUMP_RESULTS = 1 << 20
+
+
+def dump_positions(order, size, budget):
+    """batch positions of the dumped sample: the longest prefix of the seeded order whose sizes sum to at most budget,
+    sorted into batch order"""
+    return np.sort(order[:int(np.searchsorted(np.cumsum(size[order]), budget, side="right"))])
+
+
+def dump_outputs(path, rank, world, recs, d_ct, d_out, d_res):
+    """--dump-outputs: the arrays the last timed step left for its caller, one byte or status per float32 element.
+      sealed.npy  ciphertext || tag of a fixed, seeded sample of records (all of them when they fit DUMP_SEALED_BYTES),
+                  concatenated in batch order
+      opened.npy  the opened plaintext of such a sample (DUMP_OPENED_BYTES)
+      result.npy  open's per-record result (the plaintext length, or the failure code) of up to DUMP_RESULTS records
+    The sample depends on the record lengths alone, so the same arguments pick the same records in every build."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    order = np.random.default_rng(DUMP_SEED).permutation(len(recs))
+    lens = recs["len"].astype(np.int64)
+
+    def sample(buf, off, size, budget):
+        pick = dump_positions(order, size, budget)
+        size = size[pick]
+        start = np.cumsum(size) - size  # where each picked record begins in the file
+        idx = np.repeat(off[pick].astype(np.int64) - start, size) + np.arange(int(size.sum()), dtype=np.int64)
+        return buf[torch.from_numpy(idx).to(buf.device)].cpu().numpy().astype(np.float32)
+
+    arrays = {"sealed": sample(d_ct, recs["out_off"], lens + 16, DUMP_SEALED_BYTES),
+              "opened": sample(d_out, recs["in_off"], lens, DUMP_OPENED_BYTES),
+              "result": d_res[torch.from_numpy(np.sort(order[:DUMP_RESULTS])).to(d_res.device)].cpu().numpy().astype(np.float32)}
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
+    return {name + suffix + ".npy": int(a.size) for name, a in arrays.items()}
+
+
+def headline(args, cfg, world, n, aad_len, lanes, elapsed, setup_s):
+    """the fields every result line has; report_ranks adds value and the per-rank rates"""
+    return {
+        "metric": "GiB/s AES-128-GCM seal+open, device-resident, 16KiB records, 1/2/4/8 GPU"
+        if args.config == "c2" else f"GiB/s AES-GCM seal+open, device-resident ({args.config})",
+        "value": None,
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "full": args.full,
+        "data": "synthetic (splitmix64 records, SURVEY.md §8(d)), generated in HBM",
+        "config": {"workload": cfg["desc"], "records_per_gpu": n, "record_bytes": cfg["L"] or "mixed 64-16384",
+                   "aad_bytes": aad_len, "keys": cfg["keys"], "key_bits": cfg["key_len"] * 8,
+                   "lanes_per_record": lanes, "record_align": record_align(args.align),
+                   "parallelism": (f"records sharded by range over {world} GPU(s), no collective" if args.scaling == "weak" else
+                                   f"one batch of {cfg['n']} records split over {world} GPU(s) in byte-balanced contiguous "
+                                   f"ranges, no collective")},
+        "key_setup_s": round(setup_s, 4),
+    }
+
+
 def report_ranks(result, per_rank, world, steps, elapsed):
     """per-rank and whole-node rates from every rank's [seconds, plaintext bytes per step, seal ms, open ms, first record,
     end record, golden records checked]: whole node = sum of all ranks' bytes / the slowest rank's time"""
@@ -740,6 +817,11 @@ def main():
     ap.add_argument("--node-e2e", default="",
                     help="only the host-resident path over these devices in one process (ptls_hip_node_*), e.g. 0,1,2,3; "
                          "a device may repeat (one-GPU rehearsal: 0,0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure (parity, per-kernel times, "
+                         "roofline, host-resident paths, plugin, CPU baseline); the --no-* options trim that set")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32; a fixed, seeded sample)")
     ap.add_argument("--dry-run", action="store_true", help=argparse.SUPPRESS)  # CPU rehearsal of the rank logic (tests)
     args = ap.parse_args()
     launch_ranks(args)  # N > 1 without a launcher: re-run as N ranks, before any GPU call
@@ -783,7 +865,7 @@ def main():
     ks.set(0, keys, ivs)
     setup_s = time.time() - t0
     secrets_s = None
-    if cfg["keys"] > 1:
+    if args.full and cfg["keys"] > 1:
         # the same number of connections keyed from TLS 1.3 traffic secrets on the GPU
         hs = 48 if cfg["key_len"] == 32 else 32
         ks2 = ptls_hip.KeySet(eng, cfg["key_len"], cfg["keys"])
@@ -841,6 +923,20 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = max_over_ranks(time.perf_counter() - t0, world)
+    dumped = dump_outputs(args.dump_outputs, rank, world, recs, d_ct, d_out, d_res) if args.dump_outputs else None
+    if not args.full:
+        result = headline(args, cfg, world, n, aad_len, seal_b.lanes, elapsed, setup_s)
+        report_ranks(result, gather_ranks([mine, float(sum_L), 0.0, 0.0, float(lo), float(hi), 0.0], world), world, args.steps,
+                     elapsed)
+        if dumped:
+            result["outputs_dumped"] = dumped
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        for o in (seal_b, open_b, ks, eng):
+            o.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # per-kernel timing (HIP events on the launch stream) and the clock of those same launches, outside the timed
     # region: the kernels' diagnostic stamps (ptls_hip_batch_set_clock) give delta(shader cycles) / delta(100 MHz
@@ -875,26 +971,8 @@ def main():
     achieved = alg_bytes / (seal_ms * 1e-3) / 1e9
     batch_kernel = seal_b.lanes != 64
 
-    result = {
-        "metric": "GiB/s AES-128-GCM seal+open, device-resident, 16KiB records, 1/2/4/8 GPU"
-        if args.config == "c2" else f"GiB/s AES-GCM seal+open, device-resident ({args.config})",
-        "value": None,
-        "unit": "GiB/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (splitmix64 records, SURVEY.md §8(d)), generated in HBM",
-        "config": {"workload": cfg["desc"], "records_per_gpu": n, "record_bytes": cfg["L"] or "mixed 64-16384",
-                   "aad_bytes": aad_len, "keys": cfg["keys"], "key_bits": cfg["key_len"] * 8,
-                   "lanes_per_record": seal_b.lanes, "record_align": record_align(args.align),
-                   "parallelism": (f"records sharded by range over {world} GPU(s), no collective" if args.scaling == "weak" else
-                                   f"one batch of {cfg['n']} records split over {world} GPU(s) in byte-balanced contiguous "
-                                   f"ranges, no collective")},
+    result = headline(args, cfg, world, n, aad_len, seal_b.lanes, elapsed, setup_s)
+    result.update({
         "seal_gibps": round(sum(r[1] / (r[2] * 1e-3) for r in per_rank) / GIB, 2),
         "open_gibps": round(sum(r[1] / (r[3] * 1e-3) for r in per_rank) / GIB, 2),
         "seal_ms": round(seal_ms, 3),
@@ -916,7 +994,6 @@ def main():
                          "timed_loop_seal_open_ms": round(timed_seal_open_ms, 3),
                          "source": "s_memtime / s_memrealtime at each workgroup's start and end, in the launches "
                                    "seal_ms / open_ms were timed on (not in the timed loop)"},
-        "key_setup_s": round(setup_s, 4),
         "key_setup_from_secrets_s": None if secrets_s is None else round(secrets_s, 4),
         "roofline": {"bound": "lds" if batch_kernel else "latency", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": None,
@@ -927,8 +1004,10 @@ def main():
                      "algorithmic_bytes_per_launch": alg_bytes},
         "parity": {"open_all_ok": ok_open, "roundtrip_bytes_equal": ok_pt, "golden_records_checked": int(sum(r[6] for r in per_rank)),
                    "golden_records_checked_per_rank": [int(r[6]) for r in per_rank]},
-    }
+    })
     report_ranks(result, per_rank, world, args.steps, elapsed)
+    if dumped:
+        result["outputs_dumped"] = dumped
     copy_gbs, torch_copy_gbs = device_copy_gbs(eng)
     result["roofline"]["measured_copy_gbs"] = copy_gbs
     result["roofline"]["measured_copy_source"] = ("ptls_hip_device_copy: one 16-B load + store per thread, 4 GiB, read + "

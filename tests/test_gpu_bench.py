@@ -1,4 +1,4 @@
-"""The multi-rank bench path on hardware (never run on a GPU before round 3): `bench.py --gpus 2` starts
+"""The multi-rank bench path on hardware (never run on a GPU before round 3): `bench.py --full --gpus 2` starts
 its own two ranks (torch.distributed.run, gloo for the barriers and the timing summary, no RCCL), here both on device 0
 (--device 0), each sealing / opening its own shard of configs[4] and checking its sealed records against the
 lib/fusion.c digests of tests/golden/configs.json; rank 0 then times the reference's CPU engines with the GPUs idle, so
@@ -26,7 +26,7 @@ def _bench(*args, timeout=300):
 
 
 def test_bench_two_ranks_on_one_device():
-    rc, lines, err = _bench("--gpus", "2", "--device", "0", "--config", "c5", "--records", "65536", "--steps", "2",
+    rc, lines, err = _bench("--full", "--gpus", "2", "--device", "0", "--config", "c5", "--records", "65536", "--steps", "2",
                             "--warmup", "1", "--cpu-sample-mib", "64", "--e2e-records", "20000", "--no-plugin")
     assert rc == 0, err[-4000:]
     assert len(lines) == 1
@@ -47,6 +47,44 @@ def test_bench_two_ranks_on_one_device():
     assert c["kind"] == "reference" and c["cores"] >= 1 and c["value"] > 0, c
     x = c["full_host_extrapolation"]
     assert x["kind"].startswith("extrapolation") and x["physical_cores"] >= c["cores"] and x["gibps"] > c["single_core"]
+
+
+def test_plain_run_times_the_steps_and_dumps_its_outputs(tmp_path):
+    """A plain `bench.py` run holds the headline fields and none of --full's measurements, and --dump-outputs writes what
+    its last step produced: the sealed records (here all 4096, the first 64 compared with the lib/fusion.c digests of
+    tests/golden/configs.json), a seeded sample of the opened plaintext (== the generator's bytes) and open's results."""
+    import hashlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n, L = 4096, 1350
+    rc, lines, err = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "c3", "--records", str(n),
+                            "--dump-outputs", str(tmp_path))
+    assert rc == 0, err[-4000:]
+    assert len(lines) == 1
+    r = lines[0]
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["n_gpus"] == 1 and r["full"] is False
+    assert r["unit"] == "GiB/s" and r["higher_is_better"] is True and r["dtype"] == "u8" and "seal+open" in r["metric"]
+    assert r["ms_per_step"] > 0
+    assert abs(r["value"] - 2 * n * L / (r["ms_per_step"] * 1e-3) / (1 << 30)) <= 0.02 * r["value"] + 0.01
+    for k in ("parity", "roofline", "cpu_baseline", "host_e2e", "plugin_ptlsbench", "clock_in_run", "seal_ms"):
+        assert k not in r, k
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["opened.npy", "result.npy", "sealed.npy"] == sorted(r["outputs_dumped"])
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64_000_000
+    sealed, opened, result = (np.load(tmp_path / f"{k}.npy") for k in ("sealed", "opened", "result"))
+    assert sealed.dtype == opened.dtype == result.dtype == np.float32
+    assert np.array_equal(result, np.full(n, L, dtype=np.float32))
+    assert sealed.shape == (n * (L + 16),)  # every record fits the sealed sample
+    golden = bench.golden_digests("c3")
+    ct = sealed.astype(np.uint8).reshape(n, L + 16)
+    for i in range(64):
+        assert hashlib.sha256(ct[i].tobytes()).hexdigest() == golden[i], i
+    order = np.random.default_rng(bench.DUMP_SEED).permutation(n)
+    pick = bench.dump_positions(order, np.full(n, L, dtype=np.int64), bench.DUMP_OPENED_BYTES)
+    assert 0 < len(pick) < n  # a sample
+    expect = bench.stream_bytes(np.uint64(bench.SEED_DATA) ^ pick.astype(np.uint64), L)
+    assert np.array_equal(opened.astype(np.uint8).reshape(len(pick), L), expect)
 
 
 def test_bench_node_e2e_device_listed_twice():

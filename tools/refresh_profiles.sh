@@ -17,6 +17,7 @@ for c in $cfgs; do
   cp gpurun_out/pmc_$c/lds_$c.json profiles/lds_$c.json
   cp gpurun_out/prof_${tag}_$c/traffic_$c.json profiles/traffic_$c.json
   echo "=== $c bench"
-  timeout -k 10 300 python bench.py --config $c > gpurun_out/bench_${c}_full.log 2>&1
+  mkdir -p "${BENCH_LOG_DIR:-bench_logs}"  # the full bench lines go here; tools/collect_profiles.sh reads the same variable
+  timeout -k 10 300 python bench.py --full --config $c > "${BENCH_LOG_DIR:-bench_logs}/bench_${c}_full.log" 2>&1
 done
 echo done
