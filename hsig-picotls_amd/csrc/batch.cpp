@@ -59,6 +59,7 @@ extern "C" ptls_hip_batch_t *ptls_hip_batch_new(ptls_hip_engine_t *eng, const pt
     for (size_t i = 0; i < n; ++i)
         b->max_key = std::max(b->max_key, recs[i].key);
     b->auto_lanes = b->lanes = choose_lanes(b->h_recs.data(), b->h_recs.size(), (unsigned)eng->ncu);
+    b->chacha_auto_lanes = b->chacha_lanes = choose_chacha_lanes(b->h_recs.data(), b->h_recs.size(), (unsigned)eng->ncu);
     if (n != 0) {
         if (dev_alloc(eng, reinterpret_cast<void **>(&b->d_recs), n * sizeof(ptls_hip_record_t)) != hipSuccess ||
             hipMemcpy(b->d_recs, recs, n * sizeof(ptls_hip_record_t), hipMemcpyHostToDevice) != hipSuccess) {
@@ -158,10 +159,49 @@ extern "C" int ptls_hip_batch_set_clock(ptls_hip_batch_t *b, void *d_buf, size_t
 }
 
 int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result,
-              void *stream, bool open, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, void *mask)
+              void *stream, bool open, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, void *mask, int algo)
 {
     if (b == nullptr || ks == nullptr || ks->eng != b->eng)
         return fail(PTLS_HIP_EINVAL, "seal/open: batch and keyset must belong to the same engine");
+    /* the keyset's kind is host state: a call of the other cipher fails here, before any slot memory is named */
+    if (algo != 0 && ks->algo != algo)
+        return fail(PTLS_HIP_EINVAL, "seal/open: the keyset holds %s keys",
+                    ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305 ? "ChaCha20-Poly1305" : "AES-GCM");
+    if (supp != nullptr && hp_ks != nullptr && hp_ks->algo != ks->algo)
+        return fail(PTLS_HIP_EINVAL, "seal_batch_supp: the header-protection keyset is of the other algorithm");
+    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
+        if (supp != nullptr && (hp_ks == nullptr || hp_ks->eng != b->eng || mask == nullptr))
+            return fail(PTLS_HIP_EINVAL, "seal_batch_supp: the header-protection keyset must be on the same engine, and mask "
+                                         "must be given");
+        if (b->n == 0)
+            return 0;
+        if (b->max_key >= ks->nslots)
+            return fail(PTLS_HIP_EINVAL, "seal/open: a record names key slot %u, the keyset has %zu", b->max_key, ks->nslots);
+        if (in == nullptr || out == nullptr || (open && result == nullptr))
+            return fail(PTLS_HIP_EINVAL, "seal/open: null buffer");
+        DeviceGuard g(b->eng->device);
+        ChaChaArgs a{};
+        a.recs = b->d_recs; /* descriptor order: no key runs, no chunks */
+        a.n = b->n;
+        a.in = static_cast<const uint8_t *>(in);
+        a.aad = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
+        a.out = static_cast<uint8_t *>(out);
+        a.result = result;
+        a.slots = ks->d_chacha;
+        a.supp = supp;
+        a.hp_slots = hp_ks != nullptr ? hp_ks->d_chacha : nullptr;
+        a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
+        a.mask = static_cast<uint8_t *>(mask);
+        const bool base_aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(a.aad) |
+                                    reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+        const int e = launch_chacha_batch(b->chacha_lanes, open, stream, a, base_aligned && b->all_aligned);
+        if (e != 0)
+            return fail(PTLS_HIP_ELAUNCH, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        keyset_note_use(ks, stream);
+        keyset_note_use(hp_ks, stream);
+        b->uses.note(stream);
+        return 0;
+    }
     if (supp != nullptr && (hp_ks == nullptr || hp_ks->eng != b->eng || hp_ks->key_size != ks->key_size || mask == nullptr))
         return fail(PTLS_HIP_EINVAL, "seal_batch_supp: the header-protection keyset must be on the same engine with the "
                                      "AEAD's key size, and mask must be given");
@@ -211,7 +251,61 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
 extern "C" int ptls_hip_aesgcm_seal_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out,
                                           void *stream)
 {
-    return run_batch(b, ks, in, aad, out, nullptr, stream, false);
+    return run_batch(b, ks, in, aad, out, nullptr, stream, false, nullptr, nullptr, nullptr, PTLS_HIP_ALGO_AESGCM);
+}
+
+/* ---- ChaCha20-Poly1305 (chacha_kernel.hip): the same batches, the keyset's other kind ---- */
+
+extern "C" int ptls_hip_batch_set_chacha_lanes(ptls_hip_batch_t *b, int lanes)
+{
+    if (b == nullptr || !(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64))
+        return fail(PTLS_HIP_EINVAL, "batch_set_chacha_lanes: lanes must be 0, 1, 4, 16 or 64");
+    b->chacha_lanes = lanes == 0 ? b->chacha_auto_lanes : lanes; /* nothing is planned per width: the next launch uses it */
+    return 0;
+}
+
+extern "C" int ptls_hip_batch_chacha_lanes(ptls_hip_batch_t *b)
+{
+    return b != nullptr ? b->chacha_lanes : fail(PTLS_HIP_EINVAL, "batch_chacha_lanes: null batch");
+}
+
+extern "C" int ptls_hip_chacha20poly1305_seal_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad,
+                                                    void *out, void *stream)
+{
+    return run_batch(b, ks, in, aad, out, nullptr, stream, false, nullptr, nullptr, nullptr, PTLS_HIP_ALGO_CHACHA20POLY1305);
+}
+
+extern "C" int ptls_hip_chacha20poly1305_open_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad,
+                                                    void *out, uint64_t *result, void *stream)
+{
+    return run_batch(b, ks, in, aad, out, result, stream, true, nullptr, nullptr, nullptr, PTLS_HIP_ALGO_CHACHA20POLY1305);
+}
+
+extern "C" int ptls_hip_chacha20poly1305_seal_batch_supp(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                                         const ptls_hip_supp_t *supp, const void *in, const void *aad, void *out,
+                                                         void *mask, void *stream)
+{
+    if (supp == nullptr)
+        return fail(PTLS_HIP_EINVAL, "seal_batch_supp: supp descriptors missing");
+    return run_batch(b, ks, in, aad, out, nullptr, stream, false, hp_ks, supp, mask, PTLS_HIP_ALGO_CHACHA20POLY1305);
+}
+
+extern "C" int ptls_hip_chacha20_mask_batch(ptls_hip_engine_t *eng, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
+                                            const void *src, void *mask, void *stream)
+{
+    if (eng == nullptr || hp_ks == nullptr || hp_ks->eng != eng || hp_ks->algo != PTLS_HIP_ALGO_CHACHA20POLY1305 ||
+        n > 0xffffffffu || (n != 0 && (supp == nullptr || src == nullptr || mask == nullptr)))
+        return fail(PTLS_HIP_EINVAL, "chacha20_mask_batch: bad arguments (a ChaCha keyset of this engine is needed)");
+    if (n == 0)
+        return 0;
+    DeviceGuard g(eng->device);
+    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)eng->ncu * 4);
+    const int e = launch_chacha_mask(supp, (uint32_t)n, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(mask),
+                                     hp_ks->d_chacha, (uint32_t)hp_ks->nslots, grid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "chacha20_mask_batch: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    keyset_note_use(hp_ks, stream);
+    return 0;
 }
 
 extern "C" int ptls_hip_aesgcm_seal_batch_supp(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
@@ -220,13 +314,13 @@ extern "C" int ptls_hip_aesgcm_seal_batch_supp(ptls_hip_batch_t *b, ptls_hip_key
 {
     if (supp == nullptr)
         return fail(PTLS_HIP_EINVAL, "seal_batch_supp: supp descriptors missing");
-    return run_batch(b, ks, in, aad, out, nullptr, stream, false, hp_ks, supp, mask);
+    return run_batch(b, ks, in, aad, out, nullptr, stream, false, hp_ks, supp, mask, PTLS_HIP_ALGO_AESGCM);
 }
 
 extern "C" int ptls_hip_aesecb_batch(ptls_hip_engine_t *eng, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
                                      const void *src, void *mask, void *stream)
 {
-    if (eng == nullptr || hp_ks == nullptr || hp_ks->eng != eng || n > 0xffffffffu ||
+    if (eng == nullptr || hp_ks == nullptr || hp_ks->eng != eng || hp_ks->algo != PTLS_HIP_ALGO_AESGCM || n > 0xffffffffu ||
         (n != 0 && (supp == nullptr || src == nullptr || mask == nullptr)))
         return fail(PTLS_HIP_EINVAL, "aesecb_batch: bad arguments");
     if (n == 0)
@@ -245,7 +339,7 @@ extern "C" int ptls_hip_aesecb_batch(ptls_hip_engine_t *eng, ptls_hip_keyset_t *
 extern "C" int ptls_hip_aesgcm_open_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out,
                                           uint64_t *result, void *stream)
 {
-    return run_batch(b, ks, in, aad, out, result, stream, true);
+    return run_batch(b, ks, in, aad, out, result, stream, true, nullptr, nullptr, nullptr, PTLS_HIP_ALGO_AESGCM);
 }
 
 extern "C" int ptls_hip_fill_records(ptls_hip_batch_t *b, void *buf, uint64_t seed, uint64_t index_base, const uint64_t *index,

@@ -3,7 +3,7 @@
  * visibility, so the library exports only include/ptls_hip.h).
  *
  *   engine.cpp         errors, the AES T-table, engines (device memory pool, chunk queues), the start-up self-check
- *   keyset.cpp         keysets: key slots + GHASH basis, keys / IVs / TLS 1.3 secrets
+ *   keyset.cpp         keysets: AES key slots + GHASH basis, or ChaCha key slots; keys / IVs / TLS 1.3 secrets
  *   planner.cpp        the launch planner: lanes per record, chunks, grid
  *   batch.cpp          batches and the device-resident seal / open / header-protection calls
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
@@ -110,8 +110,10 @@ struct Uses {
 struct st_ptls_hip_keyset_t {
     ptls_hip_engine_t *eng;
     size_t key_size, nslots;
-    KeySlot *d_slots;
-    uint32_t *d_basis;
+    int algo = PTLS_HIP_ALGO_AESGCM; /* PTLS_HIP_ALGO_*: which of the two slot arrays below exists */
+    KeySlot *d_slots;     /* AES-GCM: key schedule, IV, H powers */
+    uint32_t *d_basis;    /* AES-GCM: the GHASH basis */
+    ChaChaSlot *d_chacha = nullptr; /* ChaCha20-Poly1305: key + IV, 44 bytes per slot (no basis, no KeySlot) */
     std::vector<uint8_t> ivs; /* host mirror of every slot's static IV (do_get_iv) */
     int64_t pool_id = -1;     /* >= 0: a plugin context's slot from the plugin pool (pool_keyset), not its own allocation */
     Uses uses; /* launches that read this keyset: keyset_free waits for exactly that work */
@@ -139,6 +141,8 @@ struct st_ptls_hip_batch_t {
     bool all_aligned; /* every descriptor's in/out/aad offset is a multiple of 16 */
     int auto_lanes; /* chosen from the record lengths */
     bool forced;
+    int chacha_lanes;      /* lanes per record of the ChaCha kernel, in use (1, 4, 16, 64) */
+    int chacha_auto_lanes; /* chosen from the record lengths */
     uint32_t max_key; /* largest key slot any record names (checked against the keyset at seal/open) */
     unsigned max_wg;  /* 0, or a cap on the workgroups of a launch (planning then sizes chunks for that many) */
     uint64_t *d_clk;  /* diagnostic clock stamps of the next launches (ptls_hip_batch_set_clock), or nullptr */
@@ -187,6 +191,7 @@ uint32_t *queue_slot(ptls_hip_engine_t *e);
 
 /* ---- planner.cpp ---- */
 int choose_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu);
+int choose_chacha_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu);
 unsigned plan_grid(size_t n, size_t nchunks, int lanes, unsigned ncu);
 int plan_wg(const std::vector<Chunk> &ch, int lanes);
 void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned ncu, std::vector<Chunk> &ch,
@@ -194,10 +199,11 @@ void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned n
 bool identity_order(const std::vector<uint32_t> &order, size_t n);
 
 /* ---- batch.cpp ---- */
-/* one asynchronous seal / open launch of a planned batch (the device-resident calls and the TLS 1.3 ones) */
+/* one asynchronous seal / open launch of a planned batch (the device-resident calls and the TLS 1.3 ones), with the
+ * kernel of the keyset's algorithm; algo != 0: the keyset (and the header-protection keyset) must be of that algorithm */
 int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result,
               void *stream, bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr,
-              void *mask = nullptr);
+              void *mask = nullptr, int algo = 0);
 
 /* ---- plugin_worker.cpp ---- */
 /* ptls_hip_keyset_free of a plugin context's pooled slot */

@@ -180,6 +180,39 @@ int launch_fill(const ptls_hip_record_t *recs, uint32_t n, uint8_t *buf, uint64_
 int launch_copy16(void *dst, const void *src, size_t n16, void *stream);
 int launch_gap_scatter(const GapPiece *pieces, uint32_t n, const uint8_t *src, uint8_t *dst, void *stream);
 
+/* ---- ChaCha20-Poly1305 (chacha_kernel.hip) ---- */
+
+/* a ChaCha key slot: the 32-byte key and the 12-byte static IV as little-endian words.  r belongs to the record, not to
+ * the key, so there is no expanded form. */
+struct ChaChaSlot {
+    uint32_t key[8];
+    uint32_t iv[3];
+};
+static_assert(sizeof(ChaChaSlot) == 44, "ChaChaSlot: 44 bytes");
+
+struct ChaChaArgs {
+    const ptls_hip_record_t *recs; /* descriptor order; nullptr: the one record `one`, by value (the plugin's calls) */
+    uint64_t n;
+    const uint8_t *in;
+    const uint8_t *aad;
+    uint8_t *out;
+    uint64_t *result; /* open only */
+    const ChaChaSlot *slots;
+    /* seal only, optional: header-protection masks (ptls_hip_chacha20poly1305_seal_batch_supp) */
+    const ptls_hip_supp_t *supp;
+    const ChaChaSlot *hp_slots;
+    uint32_t hp_nslots;
+    uint8_t *mask;
+    ptls_hip_record_t one;
+};
+
+/* lanes: 1, 4, 16 or 64 per record */
+int launch_chacha_batch(int lanes, bool open, void *stream, const ChaChaArgs &a, bool aligned);
+int launch_chacha_mask(const ptls_hip_supp_t *supp, uint32_t n, const uint8_t *src, uint8_t *mask, const ChaChaSlot *hp_slots,
+                       uint32_t hp_nslots, unsigned grid, void *stream);
+int launch_chacha_keysetup(ChaChaSlot *slots, const uint8_t *keys, const uint8_t *ivs, uint32_t first, uint32_t count,
+                           void *stream);
+
 } // namespace ptls_hip
 
 #endif

@@ -1,5 +1,6 @@
 /*
- * keyset.cpp -- keysets: arrays of device-resident AEAD contexts (KeySlot + GHASH basis, internal.h), keyed from raw keys
+ * keyset.cpp -- keysets: arrays of device-resident AEAD contexts (AES-GCM: KeySlot + GHASH basis; ChaCha20-Poly1305:
+ * ChaChaSlot, internal.h), keyed from raw keys
  * (setup_crypto, lib/fusion.c:1184-1206) or from TLS 1.3 traffic secrets (get_traffic_keys, lib/picotls.c:1603-1622),
  * with the static-IV get / set / xor of ptls_aead_xor_iv (lib/picotls.c:6481-6490).
  */
@@ -43,11 +44,54 @@ extern "C" ptls_hip_keyset_t *ptls_hip_keyset_new(ptls_hip_engine_t *eng, size_t
 
 
 
+/* A ChaCha20-Poly1305 keyset: 44 bytes per slot (key + static IV) in its own device array; no KeySlot, no GHASH basis. */
+extern "C" ptls_hip_keyset_t *ptls_hip_keyset_new_algo(ptls_hip_engine_t *eng, int algo, size_t key_size, size_t nslots)
+{
+    if (algo == PTLS_HIP_ALGO_AESGCM)
+        return ptls_hip_keyset_new(eng, key_size, nslots);
+    if (eng == nullptr || algo != PTLS_HIP_ALGO_CHACHA20POLY1305 || key_size != 32 || nslots == 0 || nslots > 0xffffffffu) {
+        fail(PTLS_HIP_EINVAL, "keyset_new_algo: bad arguments (algo %d, key_size %zu, nslots %zu)", algo, key_size, nslots);
+        return nullptr;
+    }
+    DeviceGuard g(eng->device);
+    auto *ks = new st_ptls_hip_keyset_t();
+    ks->eng = eng;
+    ks->algo = PTLS_HIP_ALGO_CHACHA20POLY1305;
+    ks->key_size = key_size;
+    ks->nslots = nslots;
+    ks->d_slots = nullptr;
+    ks->d_basis = nullptr;
+    ks->ivs.assign(nslots * 12, 0);
+    if (dev_alloc(eng, reinterpret_cast<void **>(&ks->d_chacha), nslots * sizeof(ChaChaSlot)) != hipSuccess) {
+        fail(PTLS_HIP_ENOMEM, "keyset_new_algo: cannot allocate %zu key slots", nslots);
+        delete ks;
+        return nullptr;
+    }
+    (void)hipMemsetAsync(ks->d_chacha, 0, nslots * sizeof(ChaChaSlot), eng->util);
+    (void)hipStreamSynchronize(eng->util);
+    return ks;
+}
+
+extern "C" int ptls_hip_keyset_algo(ptls_hip_keyset_t *ks)
+{
+    return ks != nullptr ? ks->algo : fail(PTLS_HIP_EINVAL, "keyset_algo: null keyset");
+}
+
 extern "C" void ptls_hip_keyset_free(ptls_hip_keyset_t *ks)
 {
     if (ks == nullptr)
         return;
     DeviceGuard g(ks->eng->device);
+    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
+        ks->uses.wait();
+        ptls_hip_engine_t *e = ks->eng;
+        (void)hipMemsetAsync(ks->d_chacha, 0, ks->nslots * sizeof(ChaChaSlot), e->util); /* zeroize before release */
+        dev_free(e, ks->d_chacha);
+        (void)hipStreamSynchronize(e->util);
+        std::fill(ks->ivs.begin(), ks->ivs.end(), 0);
+        delete ks;
+        return;
+    }
     if (ks->pool_id >= 0) { /* a plugin context's pooled slot: zeroed and retired, nothing waits */
         pool_release(ks);
         std::fill(ks->ivs.begin(), ks->ivs.end(), 0);
@@ -74,6 +118,15 @@ extern "C" size_t ptls_hip_keyset_size(ptls_hip_keyset_t *ks)
     return ks->nslots;
 }
 
+/* raw keys and IVs in device memory -> the keyset's slots: the AES key expansion and GHASH basis, or ChaCha's plain copy */
+static int keyset_setup(ptls_hip_keyset_t *ks, const uint8_t *d_keys, const uint8_t *d_ivs, uint32_t first, uint32_t count,
+                        void *stream)
+{
+    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305)
+        return launch_chacha_keysetup(ks->d_chacha, d_keys, d_ivs, first, count, stream);
+    return launch_keysetup(ks->d_slots, ks->d_basis, d_keys, d_ivs, first, count, (int)ks->key_size, ks->eng->d_t0, stream);
+}
+
 extern "C" int ptls_hip_keyset_set(ptls_hip_keyset_t *ks, size_t first, size_t count, const void *keys, const void *ivs,
                                    void *stream)
 {
@@ -98,8 +151,7 @@ extern "C" int ptls_hip_keyset_set(ptls_hip_keyset_t *ks, size_t first, size_t c
         hipMemcpyAsync(d_tmp + kbytes, ivs, ibytes, hipMemcpyHostToDevice, s) != hipSuccess) {
         rc = fail(PTLS_HIP_ENODEV, "keyset_set: upload failed");
     } else {
-        int e = launch_keysetup(ks->d_slots, ks->d_basis, d_tmp, d_tmp + kbytes, (uint32_t)first, (uint32_t)count,
-                                (int)ks->key_size, ks->eng->d_t0, stream);
+        int e = keyset_setup(ks, d_tmp, d_tmp + kbytes, (uint32_t)first, (uint32_t)count, stream);
         if (e != 0)
             rc = fail(PTLS_HIP_ELAUNCH, "keyset_set: key setup launch failed: %s", hipGetErrorString((hipError_t)e));
         else if (hipStreamSynchronize(s) != hipSuccess)
@@ -137,8 +189,7 @@ static int keyset_from_secrets(ptls_hip_keyset_t *ks, size_t first, size_t count
     } else if (int e = launch_derive_traffic_keys(d_sec, update ? d_next : nullptr, (uint32_t)count, (int)hash_size,
                                                   (int)ks->key_size, update ? 1 : 0, d_keys, d_ivs, stream)) {
         rc = fail(PTLS_HIP_ELAUNCH, "keyset secrets: derive launch failed: %s", hipGetErrorString((hipError_t)e));
-    } else if (int e2 = launch_keysetup(ks->d_slots, ks->d_basis, d_keys, d_ivs, (uint32_t)first, (uint32_t)count,
-                                        (int)ks->key_size, ks->eng->d_t0, stream)) {
+    } else if (int e2 = keyset_setup(ks, d_keys, d_ivs, (uint32_t)first, (uint32_t)count, stream)) {
         rc = fail(PTLS_HIP_ELAUNCH, "keyset secrets: key setup launch failed: %s", hipGetErrorString((hipError_t)e2));
     } else if (hipMemcpyAsync(h_ivs.data(), d_ivs, ibytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
                (update && hipMemcpyAsync(secrets, d_next, sbytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
@@ -182,7 +233,9 @@ extern "C" int ptls_hip_keyset_set_iv(ptls_hip_keyset_t *ks, size_t slot, const 
     DeviceGuard g(ks->eng->device);
     std::memcpy(&ks->ivs[slot * 12], iv, 12);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemcpyAsync(&ks->d_slots[slot].iv, &ks->ivs[slot * 12], 12, hipMemcpyHostToDevice, s), PTLS_HIP_ENODEV);
+    void *d_iv = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305 ? static_cast<void *>(&ks->d_chacha[slot].iv)
+                                                            : static_cast<void *>(&ks->d_slots[slot].iv);
+    HIP_TRY(hipMemcpyAsync(d_iv, &ks->ivs[slot * 12], 12, hipMemcpyHostToDevice, s), PTLS_HIP_ENODEV);
     HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
     return 0;
 }

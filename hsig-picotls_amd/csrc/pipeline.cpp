@@ -341,6 +341,9 @@ static int pipeline_run(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, const ptl
                         const void *h_aad, void *h_out, uint64_t *h_result, PipeMode mode, ptls_hip_keyset_t *hp_ks = nullptr,
                         const ptls_hip_supp_t *supp = nullptr, void *h_mask = nullptr)
 {
+    /* the host transports plan their launches for the AES-GCM kernels only */
+    if ((ks != nullptr && ks->algo != PTLS_HIP_ALGO_AESGCM) || (hp_ks != nullptr && hp_ks->algo != PTLS_HIP_ALGO_AESGCM))
+        return fail(PTLS_HIP_EINVAL, "pipeline: ChaCha20-Poly1305 keysets are served by the device-resident batch calls only");
     if (supp != nullptr && (mode != PIPE_SEAL || hp_ks == nullptr || ks == nullptr || hp_ks->eng != ks->eng ||
                             hp_ks->key_size != ks->key_size || h_mask == nullptr))
         return fail(PTLS_HIP_EINVAL, "pipeline_seal_supp: the header-protection keyset must be on the same engine with the "

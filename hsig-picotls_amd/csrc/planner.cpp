@@ -69,6 +69,27 @@ int choose_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu)
     return gs;
 }
 
+/* Lanes per record of the ChaCha20-Poly1305 kernel (1, 4, 16, 64).  Per record a group spends one block time on block 0
+ * and the powers of r, L / (64 G) + 1 trips, and one more for the last partial block and the tag, all G lanes wide: the
+ * lane time a record costs is G (L / (64 G) + 3), so the narrowest group that still fills the device is the cheapest
+ * (a 1 350-byte record: 24 lane blocks at G = 1, 32 at 4, 64 at 16).  Two lower bounds: enough lanes in flight for every
+ * SIMD (about 8 waves each), and a group narrower than 4 reads one record per lane, 64 bytes at a time, which no longer
+ * coalesces once records are long.  A group never gets more lanes than the mean record has whole blocks. */
+int choose_chacha_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu)
+{
+    if (n == 0)
+        return 1;
+    double sum = 0;
+    for (size_t i = 0; i < n; ++i)
+        sum += (double)(recs[i].len / 64);
+    const double blocks = sum / (double)n;
+    const double want = 2048.0 * (double)(ncu ? ncu : 256); /* lanes: 8 waves on each of a CU's 4 SIMDs */
+    int g = blocks >= 4 ? 4 : 1;
+    while (g < 64 && (double)n * g < want && blocks >= 4.0 * g)
+        g *= 4;
+    return g;
+}
+
 /* grid of a launch: one workgroup per CU at most (both kernels fill the LDS); the batch kernel takes one
  * workgroup per chunk, the sparse kernel one per 12 records (a record per wave) */
 unsigned plan_grid(size_t n, size_t nchunks, int lanes, unsigned ncu)

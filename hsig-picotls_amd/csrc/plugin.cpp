@@ -713,6 +713,261 @@ static int non_temporal_aes256gcm_setup(ptls_aead_context_t *ctx, int is_enc, co
     return non_temporal_setup(ctx, is_enc, key, iv, PTLS_AES256_KEY_SIZE);
 }
 
+/* ---------------------------------------------------------------------------------------------- */
+/* ptls_hip_chacha20poly1305 / ptls_hip_chacha20 (replace ptls_minicrypto_chacha20poly1305 / _chacha20,  */
+/* lib/cifra/chacha20.c:44-113): one launch of chacha_kernel.hip per call, never through the worker      */
+/* ---------------------------------------------------------------------------------------------- */
+
+extern "C" ptls_cipher_algorithm_t ptls_hip_chacha20;
+
+/* a one-slot ChaCha keyset of its own (44 bytes of device memory; the plugin's slot pool holds AES slots) */
+static ptls_hip_keyset_t *chacha_keyset(ptls_hip_engine_t *eng, const void *key, const void *iv)
+{
+    ptls_hip_keyset_t *ks = ptls_hip_keyset_new_algo(eng, PTLS_HIP_ALGO_CHACHA20POLY1305, PTLS_CHACHA20_KEY_SIZE, 1);
+    if (ks == nullptr)
+        return nullptr;
+    hipStream_t stream = pool_stream();
+    const int rc = ptls_hip_keyset_set(ks, 0, 1, key, iv, stream);
+    pool_stream_put(stream);
+    if (rc != 0) {
+        ptls_hip_keyset_free(ks);
+        return nullptr;
+    }
+    return ks;
+}
+
+/* the cipher's staging (a 256-B pinned piece): descriptor @0, the 16-byte iv ("sample") @32, the keystream block @48 */
+static const size_t CC_SAMPLE = 32, CC_MASK = 48;
+
+/* do_init: the first 16 keystream bytes of ChaCha20(key, counter = LE32(iv[0..4]), nonce = iv[4..16]) on the device */
+static void chacha_init(ptls_cipher_context_t *_ctx, const void *iv)
+{
+    hip_ctr_state *st = reinterpret_cast<hip_ctr_context *>(_ctx)->st;
+    DeviceGuard g(st->eng->device);
+    const ptls_hip_supp_t sp{CC_SAMPLE, CC_MASK, 0, PTLS_HIP_SUPP_ENABLE};
+    std::memcpy(st->h_stage, &sp, sizeof(sp));
+    std::memcpy(st->h_stage + CC_SAMPLE, iv, 16);
+    hipStream_t stream = pool_stream();
+    const int e = launch_chacha_mask(reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage), 1, st->d_stage, st->d_stage,
+                                     st->ks->d_chacha, 1, 1, stream);
+    if (e != 0) {
+        g_err = hipGetErrorString((hipError_t)e);
+        plugin_die("chacha20 launch");
+    }
+    plugin_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    pool_stream_put(stream);
+    std::memcpy(st->bits, st->h_stage + CC_MASK, 16);
+    std::memset(st->h_stage + CC_SAMPLE, 0, 32);
+    st->ready = true;
+}
+
+static void chacha_cipher_dispose(ptls_cipher_context_t *_ctx)
+{
+    auto *ctx = reinterpret_cast<hip_ctr_context *>(_ctx);
+    if (ctx->st == nullptr)
+        return;
+    ecb_state_free(ctx->st); /* keyset (zeroized), staging piece, keystream bits */
+    ctx->st = nullptr;
+}
+
+static int chacha20_setup(ptls_cipher_context_t *_ctx, int is_enc, const void *key)
+{
+    (void)is_enc;
+    auto *ctx = reinterpret_cast<hip_ctr_context *>(_ctx);
+    ctx->st = nullptr;
+    ptls_hip_engine_t *eng = plugin_engine();
+    if (eng == nullptr || key == nullptr)
+        return -1;
+    DeviceGuard g(eng->device);
+    auto *st = new hip_ctr_state();
+    st->eng = eng;
+    st->ks = chacha_keyset(eng, key, nullptr);
+    if (st->ks == nullptr) {
+        delete st;
+        return -1;
+    }
+    st->h_stage = pool_piece();
+    st->d_stage = mapped_or_die(st->h_stage);
+    ctx->st = st;
+    ctx->super.do_dispose = chacha_cipher_dispose;
+    ctx->super.do_init = chacha_init;
+    ctx->super.do_transform = ctr_transform; /* at most 16 bytes per do_init, as the AES objects */
+    return 0;
+}
+
+/* one record through its own launch: the record by value, its bytes in the context's pinned staging, wiped afterwards */
+static uint64_t chacha_run(hip_aead_state *st, bool open, void *output, const void *input, size_t len, uint64_t seq,
+                           const void *aad, size_t aadlen, const hip_ctr_state *hp = nullptr, uint64_t sample_off = 0,
+                           uint8_t *mask_out = nullptr)
+{
+    DeviceGuard g(st->eng->device);
+    const size_t in_len = open ? len + 16 : len, out_len = open ? len : len + 16;
+    state_reserve(st, in_len, aadlen);
+    if (st->h_stage == nullptr) {
+        st->h_stage = pool_piece();
+        st->d_stage = mapped_or_die(st->h_stage);
+    }
+    hipStream_t stream = pool_stream();
+    if (st->iv_dirty) {
+        if (ptls_hip_keyset_set_iv(st->ks, 0, st->iv, stream) != 0)
+            plugin_die("set_iv");
+        st->iv_dirty = false;
+    }
+    uint8_t *h_in = st->h_io, *h_out = st->h_io + st->cap, *h_aad = st->h_io + st->cap + st->cap + 16;
+    stage_record(h_in, h_aad, input, len, in_len, nullptr, aad, aadlen);
+    ChaChaArgs a{};
+    a.n = 1;
+    a.one.seq = seq;
+    a.one.len = (uint32_t)len;
+    a.one.aad_len = (uint32_t)aadlen;
+    a.in = st->d_io;
+    a.out = st->d_io + st->cap;
+    a.aad = st->d_io + st->cap + st->cap + 16;
+    a.result = reinterpret_cast<uint64_t *>(st->d_stage + ST_RESULT);
+    a.slots = st->ks->d_chacha;
+    if (hp != nullptr) {
+        const ptls_hip_supp_t sp{sample_off, 0, 0, PTLS_HIP_SUPP_ENABLE};
+        std::memcpy(st->h_stage + ST_SUPP, &sp, sizeof(sp));
+        a.supp = reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage + ST_SUPP);
+        a.hp_slots = hp->ks->d_chacha;
+        a.hp_nslots = 1;
+        a.mask = st->d_stage + ST_MASK;
+    }
+    /* one record: as many lanes as it has whole ChaCha blocks to give them */
+    const size_t blocks = len / 64;
+    const int lanes = blocks >= 16 ? 64 : blocks >= 4 ? 16 : blocks >= 1 ? 4 : 1;
+    const int e = launch_chacha_batch(lanes, open, stream, a, true);
+    if (e != 0) {
+        g_err = hipGetErrorString((hipError_t)e);
+        plugin_die("chacha20poly1305 launch");
+    }
+    plugin_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    pool_stream_put(stream);
+    uint64_t result = len;
+    if (open)
+        std::memcpy(&result, st->h_stage + ST_RESULT, 8);
+    if (out_len != 0)
+        std::memcpy(output, h_out, out_len);
+    if (hp != nullptr) {
+        std::memcpy(mask_out, st->h_stage + ST_MASK, 16);
+        std::memset(st->h_stage + ST_MASK, 0, 16);
+    }
+    std::memset(h_in, 0, in_len);
+    std::memset(h_out, 0, out_len);
+    return result;
+}
+
+static void chacha_aead_encrypt(ptls_aead_context_t *_ctx, void *output, const void *input, size_t inlen, uint64_t seq,
+                                const void *aad, size_t aadlen, ptls_aead_supplementary_encryption_t *supp)
+{
+    hip_aead_state *st = reinterpret_cast<hip_aead_context *>(_ctx)->st;
+    if (supp != nullptr && supp->ctx != nullptr && supp->ctx->algo == &ptls_hip_chacha20) {
+        /* our ChaCha20 context and a sample inside the output: the mask comes out of the record's launch */
+        const hip_ctr_state *cs = reinterpret_cast<const hip_ctr_context *>(supp->ctx)->st;
+        const uint8_t *in = static_cast<const uint8_t *>(supp->input), *o = static_cast<const uint8_t *>(output);
+        if (cs != nullptr && cs->eng == st->eng && in >= o && in + 16 <= o + inlen + 16) {
+            chacha_run(st, false, output, input, inlen, seq, aad, aadlen, cs, (uint64_t)(in - o), supp->output);
+            return;
+        }
+    }
+    chacha_run(st, false, output, input, inlen, seq, aad, aadlen);
+    if (supp != nullptr) { /* any other cipher context: ptls_aead__do_encrypt's order (include/picotls.h:2027-2038) */
+        supp->ctx->do_init(supp->ctx, supp->input);
+        std::memset(supp->output, 0, sizeof(supp->output));
+        supp->ctx->do_transform(supp->ctx, supp->output, supp->output, sizeof(supp->output));
+    }
+}
+
+static void chacha_aead_encrypt_v(ptls_aead_context_t *_ctx, void *output, ptls_iovec_t *input, size_t incnt, uint64_t seq,
+                                  const void *aad, size_t aadlen)
+{
+    size_t total = 0;
+    for (size_t i = 0; i < incnt; ++i)
+        total += input[i].len;
+    std::vector<uint8_t> flat(total);
+    size_t off = 0;
+    for (size_t i = 0; i < incnt; ++i) {
+        if (input[i].len != 0)
+            std::memcpy(flat.data() + off, input[i].base, input[i].len);
+        off += input[i].len;
+    }
+    chacha_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, false, output, flat.data(), total, seq, aad, aadlen);
+    std::fill(flat.begin(), flat.end(), 0);
+}
+
+static size_t chacha_aead_decrypt(ptls_aead_context_t *_ctx, void *output, const void *input, size_t inlen, uint64_t seq,
+                                  const void *aad, size_t aadlen)
+{
+    if (inlen < 16)
+        return SIZE_MAX;
+    const uint64_t r = chacha_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, true, output, input, inlen - 16, seq, aad, aadlen);
+    return r == ~(uint64_t)0 ? SIZE_MAX : (size_t)r;
+}
+
+static int chacha20poly1305_setup(ptls_aead_context_t *_ctx, int is_enc, const void *key, const void *iv)
+{
+    (void)is_enc;
+    auto *ctx = reinterpret_cast<hip_aead_context *>(_ctx);
+    if (key == nullptr) { /* IV-only setup, on a fresh context as on a keyed one (as aesgcm_setup above) */
+        if (_ctx->dispose_crypto == nullptr) {
+            ctx->st = nullptr;
+            std::memcpy(ctx->iv, iv, 12);
+            ctx->super.dispose_crypto = aead_dispose;
+            ctx->super.do_get_iv = aead_get_iv;
+            ctx->super.do_set_iv = aead_set_iv;
+            return 0;
+        }
+        aead_set_iv(_ctx, iv);
+        return 0;
+    }
+    if (_ctx->dispose_crypto != nullptr && ctx->st != nullptr)
+        aead_dispose(_ctx);
+    ctx->st = nullptr;
+    ptls_hip_engine_t *eng = plugin_engine();
+    if (eng == nullptr)
+        return -1;
+    DeviceGuard g(eng->device);
+    auto *st = new hip_aead_state();
+    st->eng = eng;
+    st->ks = chacha_keyset(eng, key, iv);
+    if (st->ks == nullptr) {
+        delete st;
+        return -1;
+    }
+    std::memcpy(st->iv, iv, 12);
+    st->iv_dirty = false;
+    ctx->st = st;
+    ctx->super.dispose_crypto = aead_dispose;
+    ctx->super.do_get_iv = aead_get_iv;
+    ctx->super.do_set_iv = aead_set_iv;
+    ctx->super.do_encrypt_init = aead_encrypt_init;
+    ctx->super.do_encrypt_update = aead_encrypt_update;
+    ctx->super.do_encrypt_final = aead_encrypt_final;
+    ctx->super.do_encrypt = chacha_aead_encrypt;
+    ctx->super.do_encrypt_v = chacha_aead_encrypt_v;
+    ctx->super.do_decrypt = chacha_aead_decrypt;
+    return 0;
+}
+
+/* Field for field the values of ptls_minicrypto_chacha20 / ptls_minicrypto_chacha20poly1305 (lib/cifra/chacha20.c:97-113). */
+extern "C" {
+ptls_cipher_algorithm_t ptls_hip_chacha20 = {"CHACHA20", PTLS_CHACHA20_KEY_SIZE, 1, PTLS_CHACHA20_IV_SIZE, sizeof(hip_ctr_context),
+                                             chacha20_setup};
+ptls_aead_algorithm_t ptls_hip_chacha20poly1305 = {"CHACHA20-POLY1305",
+                                                   PTLS_CHACHA20POLY1305_CONFIDENTIALITY_LIMIT,
+                                                   PTLS_CHACHA20POLY1305_INTEGRITY_LIMIT,
+                                                   &ptls_hip_chacha20,
+                                                   nullptr,
+                                                   PTLS_CHACHA20_KEY_SIZE,
+                                                   PTLS_CHACHA20POLY1305_IV_SIZE,
+                                                   PTLS_CHACHA20POLY1305_TAG_SIZE,
+                                                   {PTLS_TLS12_CHACHAPOLY_FIXED_IV_SIZE, PTLS_TLS12_CHACHAPOLY_RECORD_IV_SIZE},
+                                                   0,
+                                                   0,
+                                                   sizeof(hip_aead_context),
+                                                   chacha20poly1305_setup};
+}
+
 /* Field-for-field the values of ptls_fusion_aes{128,256}ctr / aes{128,256}gcm (lib/fusion.c:1219-1256). */
 extern "C" {
 ptls_cipher_algorithm_t ptls_hip_aes128ctr = {"AES128-CTR", PTLS_AES128_KEY_SIZE, 1, PTLS_AES_IV_SIZE, sizeof(hip_ctr_context),

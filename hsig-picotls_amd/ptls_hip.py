@@ -28,6 +28,8 @@ TLS13_NO_CONTENT_TYPE = (1 << 64) - 2
 TLS13_DECODE_ERROR = -50
 TLS13_SHORT_RECORD = -20  # a complete application-data record shorter than a tag (PTLS_ALERT_BAD_RECORD_MAC)
 TRANSPORT_AUTO, TRANSPORT_COPY, TRANSPORT_MAPPED = 0, 1, 2
+ALGO_AESGCM, ALGO_CHACHA20POLY1305 = 1, 2
+EINVAL = -1
 
 
 def record_tls13_type(t):
@@ -43,6 +45,8 @@ SIGNATURES = {
     "ptls_hip_engine_device": (_i, [_vp]),
     "ptls_hip_engine_cu_count": (_i, [_vp]),
     "ptls_hip_keyset_new": (_vp, [_vp, _sz, _sz]),
+    "ptls_hip_keyset_new_algo": (_vp, [_vp, _i, _sz, _sz]),
+    "ptls_hip_keyset_algo": (_i, [_vp]),
     "ptls_hip_keyset_free": (None, [_vp]),
     "ptls_hip_keyset_size": (_sz, [_vp]),
     "ptls_hip_keyset_set": (_i, [_vp, _sz, _sz, _vp, _vp, _vp]),
@@ -69,6 +73,12 @@ SIGNATURES = {
     "ptls_hip_aesgcm_open_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ptls_hip_aesgcm_seal_batch_supp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ptls_hip_aesecb_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ptls_hip_chacha20poly1305_seal_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_chacha20poly1305_open_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_chacha20poly1305_seal_batch_supp": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_chacha20_mask_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ptls_hip_batch_set_chacha_lanes": (_i, [_vp, _i]),
+    "ptls_hip_batch_chacha_lanes": (_i, [_vp]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -110,7 +120,8 @@ SIGNATURES = {
     "ptls_hip_host_page_nodes": (_sz, [_vp, _sz, _sz, _vp, _sz]),
 }
 DATA_SYMBOLS = ("ptls_hip_aes128ctr", "ptls_hip_aes128gcm", "ptls_hip_aes256ctr", "ptls_hip_aes256gcm",
-                "ptls_hip_non_temporal_aes128gcm", "ptls_hip_non_temporal_aes256gcm")
+                "ptls_hip_non_temporal_aes128gcm", "ptls_hip_non_temporal_aes256gcm",
+                "ptls_hip_chacha20poly1305", "ptls_hip_chacha20")
 
 _lib = None
 
@@ -187,6 +198,13 @@ class Engine:
         _check(lib().ptls_hip_aesecb_batch(self.ptr, hp_keyset.ptr, _ptr(supp), n, _ptr(src), _ptr(mask), _stream(stream)),
                "aesecb_batch")
 
+    def chacha20_mask(self, hp_keyset, supp, src, mask, stream=None):
+        """mask[mask_off] = the first 16 keystream bytes of ChaCha20(hp key, counter = LE32(sample[0:4]), nonce =
+        sample[4:16]) with sample = src[sample_off:+16], for every enabled device descriptor"""
+        n = supp.numel() // SUPP_DTYPE.itemsize if hasattr(supp, "numel") else len(supp)
+        _check(lib().ptls_hip_chacha20_mask_batch(self.ptr, hp_keyset.ptr, _ptr(supp), n, _ptr(src), _ptr(mask),
+                                                  _stream(stream)), "chacha20_mask_batch")
+
     def copy(self, dst, src, nbytes, stream=None):
         """ptls_hip_device_copy: the 16-byte-per-lane streaming copy (bench.py's achievable-HBM reference)"""
         _check(lib().ptls_hip_device_copy(self.ptr, _ptr(dst), _ptr(src), nbytes, _stream(stream)), "device_copy")
@@ -198,9 +216,12 @@ class Engine:
 
 
 class KeySet:
-    def __init__(self, engine, key_size, nslots):
-        self.engine, self.key_size, self.nslots = engine, key_size, nslots
-        self.ptr = lib().ptls_hip_keyset_new(engine.ptr, key_size, nslots)
+    def __init__(self, engine, key_size, nslots, algo=ALGO_AESGCM):
+        self.engine, self.key_size, self.nslots, self.algo = engine, key_size, nslots, algo
+        if algo == ALGO_AESGCM:
+            self.ptr = lib().ptls_hip_keyset_new(engine.ptr, key_size, nslots)
+        else:
+            self.ptr = lib().ptls_hip_keyset_new_algo(engine.ptr, algo, key_size, nslots)
         if not self.ptr:
             raise HipError(f"ptls_hip_keyset_new: {last_error()}")
 
@@ -302,6 +323,28 @@ class Batch:
         """seal + QUIC header-protection masks in one launch; supp: device array of SUPP_DTYPE, one per record"""
         _check(lib().ptls_hip_aesgcm_seal_batch_supp(self.ptr, keyset.ptr, hp_keyset.ptr, _ptr(supp), _ptr(inp), _ptr(aad),
                                                      _ptr(out), _ptr(mask), _stream(stream)), "seal_batch_supp")
+
+    @property
+    def chacha_lanes(self):
+        """lanes per record of the ChaCha20-Poly1305 kernel (1, 4, 16 or 64)"""
+        return lib().ptls_hip_batch_chacha_lanes(self.ptr)
+
+    def set_chacha_lanes(self, lanes):
+        _check(lib().ptls_hip_batch_set_chacha_lanes(self.ptr, lanes), "batch_set_chacha_lanes")
+
+    def chacha_seal(self, keyset, inp, aad, out, stream=None):
+        _check(lib().ptls_hip_chacha20poly1305_seal_batch(self.ptr, keyset.ptr, _ptr(inp), _ptr(aad), _ptr(out),
+                                                          _stream(stream)), "chacha20poly1305_seal_batch")
+
+    def chacha_open(self, keyset, inp, aad, out, result, stream=None):
+        _check(lib().ptls_hip_chacha20poly1305_open_batch(self.ptr, keyset.ptr, _ptr(inp), _ptr(aad), _ptr(out), _ptr(result),
+                                                          _stream(stream)), "chacha20poly1305_open_batch")
+
+    def chacha_seal_supp(self, keyset, hp_keyset, supp, inp, aad, out, mask, stream=None):
+        """seal + ChaCha20 header-protection masks in one launch; supp: device array of SUPP_DTYPE, one per record"""
+        _check(lib().ptls_hip_chacha20poly1305_seal_batch_supp(self.ptr, keyset.ptr, hp_keyset.ptr, _ptr(supp), _ptr(inp),
+                                                               _ptr(aad), _ptr(out), _ptr(mask), _stream(stream)),
+               "chacha20poly1305_seal_batch_supp")
 
     def tls13_seal(self, keyset, inp, out, stream=None):
         """records from tls13_frame(): writes headers into `out`, then seals with them as AAD"""

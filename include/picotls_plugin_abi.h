@@ -33,6 +33,14 @@ extern "C" {
 #define PTLS_AESGCM_TAG_SIZE 16
 #define PTLS_AESGCM_CONFIDENTIALITY_LIMIT 0x2000000            /* 2^25 records */
 #define PTLS_AESGCM_INTEGRITY_LIMIT UINT64_C(0x40000000000000) /* 2^54 failed opens */
+#define PTLS_CHACHA20_KEY_SIZE 32
+#define PTLS_CHACHA20_IV_SIZE 16 /* the first 32 bits are the block counter, the other 96 the nonce (include/picotls.h:88) */
+#define PTLS_CHACHA20POLY1305_IV_SIZE 12
+#define PTLS_CHACHA20POLY1305_TAG_SIZE 16
+#define PTLS_CHACHA20POLY1305_CONFIDENTIALITY_LIMIT UINT64_MAX       /* at least 2^64 */
+#define PTLS_CHACHA20POLY1305_INTEGRITY_LIMIT UINT64_C(0x1000000000) /* 2^36 */
+#define PTLS_TLS12_CHACHAPOLY_FIXED_IV_SIZE 12
+#define PTLS_TLS12_CHACHAPOLY_RECORD_IV_SIZE 0
 
 /* {pointer, length} pair used for gather input */
 typedef struct st_ptls_iovec_t {

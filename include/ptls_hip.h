@@ -62,6 +62,16 @@ extern ptls_aead_algorithm_t ptls_hip_non_temporal_aes128gcm, ptls_hip_non_tempo
  * the mask is computed inside the same kernel launch as the record, as fusion does (:636-650). */
 extern ptls_cipher_algorithm_t ptls_hip_aes128ctr, ptls_hip_aes256ctr;
 
+/* Replace ptls_minicrypto_chacha20poly1305 / ptls_minicrypto_chacha20 (lib/cifra/chacha20.c:97-113; the OpenSSL and
+ * mbedTLS backends export the same values): TLS_CHACHA20_POLY1305_SHA256's AEAD and the ChaCha20 cipher QUIC uses for
+ * header protection.  Same vtable shape as the AES objects above (do_encrypt with supp, do_encrypt_v, do_decrypt, get /
+ * set IV, dispose; key == NULL re-sets the static IV only).  The cipher follows the contract of ptls_hip_aes*ctr:
+ * do_init(iv16) computes one keystream block on the GPU (counter = LE32(iv[0..4]), nonce = iv[4..16]) and the following
+ * do_transform XORs at most 16 bytes with it.  Every call is one kernel launch of its own; the resident worker does not
+ * serve these objects (they work whatever PTLS_HIP_PLUGIN_WORKER says). */
+extern ptls_aead_algorithm_t ptls_hip_chacha20poly1305;
+extern ptls_cipher_algorithm_t ptls_hip_chacha20;
+
 /* Device ordinal used by contexts created through the plugin objects (default 0; also read from
  * the environment variable PTLS_HIP_DEVICE).  Must be called before the first context is made. */
 int ptls_hip_set_default_device(int device);
@@ -128,6 +138,17 @@ int ptls_hip_engine_cu_count(ptls_hip_engine_t *engine);
 ptls_hip_keyset_t *ptls_hip_keyset_new(ptls_hip_engine_t *engine, size_t key_size, size_t nslots);
 void ptls_hip_keyset_free(ptls_hip_keyset_t *ks); /* zeroizes device key material */
 size_t ptls_hip_keyset_size(ptls_hip_keyset_t *ks);
+/* The AEAD of a keyset.  ptls_hip_keyset_new makes AES-GCM keysets; ptls_hip_keyset_new_algo takes the algorithm:
+ * PTLS_HIP_ALGO_AESGCM with key_size 16 or 32 (the same keyset ptls_hip_keyset_new makes), or
+ * PTLS_HIP_ALGO_CHACHA20POLY1305 with key_size 32 (TLS_CHACHA20_POLY1305_SHA256; as a header-protection keyset: QUIC's
+ * ChaCha20 header protection).  A ChaCha slot is the 32-byte key and the 12-byte static IV, 44 bytes of device memory:
+ * nothing is expanded.  keyset_set / get_iv / set_iv / xor_iv / set_secrets / update_secrets (hash_size 32) / free work on
+ * both kinds; seal / open calls take the kind their name says (2a below) and fail with PTLS_HIP_EINVAL, launching
+ * nothing, on the other; the TLS 1.3 calls (2b) take either.  The host pipelines (2c) and nodes (2d) are AES-GCM only. */
+#define PTLS_HIP_ALGO_AESGCM 1
+#define PTLS_HIP_ALGO_CHACHA20POLY1305 2
+ptls_hip_keyset_t *ptls_hip_keyset_new_algo(ptls_hip_engine_t *engine, int algo, size_t key_size, size_t nslots);
+int ptls_hip_keyset_algo(ptls_hip_keyset_t *ks);
 /* Load `count` keys (count * key_size bytes) and static IVs (count * 12 bytes; NULL = zero IVs, e.g. for
  * header-protection keys) from host memory into slots [first, first + count) and expand them on the
  * device (key schedule, H = E_K(0), powers of H).
@@ -235,6 +256,33 @@ int ptls_hip_aesgcm_seal_batch_supp(ptls_hip_batch_t *batch, ptls_hip_keyset_t *
  * for n device descriptors. */
 int ptls_hip_aesecb_batch(ptls_hip_engine_t *engine, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
                           const void *src, void *mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2a. ChaCha20-Poly1305 (RFC 8439 §2.8; picotls lib/chacha20poly1305.h) over the same batches    *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The same descriptors with the same meaning as the aesgcm calls above (nonce, in place, exact bytes, result, the TLS 1.3
+ * content-type flag), on a keyset of PTLS_HIP_ALGO_CHACHA20POLY1305.  Records are taken in descriptor order: there is no
+ * per-key state to share, so batches of many keys cost nothing extra.  PTLS_HIP_EINVAL (nothing launched) on an AES keyset
+ * or when a record names a key slot outside `ks`. */
+int ptls_hip_chacha20poly1305_seal_batch(ptls_hip_batch_t *batch, ptls_hip_keyset_t *ks, const void *in, const void *aad,
+                                         void *out, void *stream);
+int ptls_hip_chacha20poly1305_open_batch(ptls_hip_batch_t *batch, ptls_hip_keyset_t *ks, const void *in, const void *aad,
+                                         void *out, uint64_t *result, void *stream);
+/* seal + QUIC ChaCha20 header-protection masks in the same launch (RFC 9001 §5.4.4): for enabled descriptors, sample = the
+ * 16 bytes at out + sample_off after the record is written, and mask + mask_off receives the first 16 keystream bytes of
+ * ChaCha20(hp key, counter = LE32(sample[0..4]), nonce = sample[4..16]) -- what ptls_aead__do_encrypt produces with a
+ * ptls_minicrypto_chacha20 supp context (include/picotls.h:2027-2038, lib/cifra/chacha20.c:44-56); QUIC uses the first 5.
+ * hp_ks is a ChaCha keyset too (its IVs are not used).  Skipped descriptors leave their mask bytes untouched. */
+int ptls_hip_chacha20poly1305_seal_batch_supp(ptls_hip_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                              const ptls_hip_supp_t *supp, const void *in, const void *aad, void *out,
+                                              void *mask, void *stream);
+/* standalone masks for n device descriptors (the receive side), the counterpart of ptls_hip_aesecb_batch */
+int ptls_hip_chacha20_mask_batch(ptls_hip_engine_t *engine, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
+                                 const void *src, void *mask, void *stream);
+/* lanes cooperating on one record in the ChaCha kernel: 1, 4, 16 or 64; 0 = automatic from the record lengths (default) */
+int ptls_hip_batch_set_chacha_lanes(ptls_hip_batch_t *batch, int lanes);
+int ptls_hip_batch_chacha_lanes(ptls_hip_batch_t *batch);
 
 /* ------------------------------------------------------------------------------------------ *
  * 2b. TLS 1.3 record layer over the batch                      *

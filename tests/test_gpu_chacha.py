@@ -1,0 +1,582 @@
+"""ChaCha20-Poly1305 on the GPU (hsig-picotls_amd/csrc/chacha_kernel.hip) through the batch API, the TLS 1.3 record layer
+and the picotls plugin objects, bit-exact against the plain-Python RFC 8439 reference (tests/chacha_ref.py) and the fixture
+recorded from picotls's own minicrypto engine (tests/golden/chacha20poly1305.json).  No tolerance anywhere.
+
+Outputs and masks always go into 0xA5-filled buffers with 1- to 64-byte gaps between the records, and the WHOLE buffer is
+compared with its expected image, so a byte written outside a record fails the test that wrote it."""
+import functools
+import hashlib
+import hmac
+import importlib.util
+import json
+import os
+import random
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import chacha_ref
+import ptls_hip
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GS = [1, 4, 16, 64]
+LENS = [0, 1, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1350, 16384, 16385]
+AADS = [0, 1, 5, 12, 13, 16, 17, 21]
+SEQS = [0, 1, (1 << 32) - 1, 1 << 32, (1 << 64) - 1]
+U64 = (1 << 64) - 1
+FILL = 0xA5
+NKEYS = 64
+
+
+def lens_of(g):
+    return LENS + [l for l in (64 * g - 1, 64 * g, 64 * g + 1, 128 * g + 1, 3 * 64 * g + 17) if l not in LENS]
+
+
+def stream(tag, n):
+    out, i = bytearray(), 0
+    while len(out) < n:
+        out += hashlib.sha256(b"%s/%d" % (tag.encode(), i)).digest()
+        i += 1
+    return bytes(out[:n])
+
+
+KEYS = [stream("gpu-chacha-key-%d" % i, 32) for i in range(NKEYS)]
+IVS = [bytes(b | 1 for b in stream("gpu-chacha-iv-%d" % i, 12)) for i in range(NKEYS)]
+PAYLOAD = stream("gpu-chacha-payload", 40000 + 64)
+AAD = stream("gpu-chacha-aad", 64)
+
+
+@functools.lru_cache(maxsize=None)
+def ref_seal(slot, seq, aad, pt):
+    return chacha_ref.seal(KEYS[slot], IVS[slot], seq, aad, pt)
+
+
+def _gold_module():
+    spec = importlib.util.spec_from_file_location("make_chacha_golden", os.path.join(ROOT, "tests", "golden",
+                                                                                     "make_chacha_golden.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
+@pytest.fixture(scope="module")
+def fixture():
+    with open(os.path.join(ROOT, "tests", "golden", "chacha20poly1305.json")) as f:
+        return json.load(f), _gold_module()
+
+
+@pytest.fixture(scope="module")
+def keyset(engine):
+    ks = ptls_hip.KeySet(engine, 32, NKEYS, algo=ptls_hip.ALGO_CHACHA20POLY1305)
+    ks.set(0, b"".join(KEYS), b"".join(IVS))
+    yield ks
+    ks.close()
+
+
+class Rec:
+    def __init__(self, slot, seq, aad, pt, flags=0):
+        self.slot, self.seq, self.aad, self.pt, self.flags = slot, seq, aad, pt, flags
+
+
+def place(sizes, aligned):
+    """offsets of consecutive pieces with gaps of 1 .. 64 bytes: odd offsets (packed at byte granularity), or 16-aligned"""
+    offs, pos = [], 0
+    for i, s in enumerate(sizes):
+        pos += 1 + (i * 7) % 64
+        if aligned:
+            pos = (pos + 15) & ~15
+        elif pos % 2 == 0:
+            pos += 1
+        offs.append(pos)
+        pos += s
+    return offs, pos + 64
+
+
+def dev(buf):
+    return torch.from_numpy(buf).cuda()
+
+
+def run(engine, keyset, recs, g, aligned, op, in_place=False, inputs=None, seqs=None, aads=None):
+    """one seal or open launch; returns (result list or None, output buffer, expected-untouched image builder data)"""
+    n = len(recs)
+    lens = [len(r.pt) for r in recs]
+    in_sizes = [l + 16 for l in lens]  # room for ct || tag either way
+    in_offs, in_total = place(in_sizes, aligned)
+    out_offs, out_total = (in_offs, in_total) if in_place else place([l + 16 for l in lens], aligned)
+    aad_offs, aad_total = place([len(r.aad) for r in recs], aligned)
+    d = np.zeros(n, dtype=ptls_hip.RECORD_DTYPE)
+    d["in_off"], d["out_off"], d["aad_off"] = in_offs, out_offs, aad_offs
+    d["seq"] = [r.seq for r in recs] if seqs is None else seqs
+    d["len"], d["aad_len"] = lens, [len(r.aad) for r in recs]
+    d["key"], d["flags"] = [r.slot for r in recs], [r.flags for r in recs]
+    h_in = np.full(in_total, FILL, np.uint8)
+    h_aad = np.full(aad_total, FILL, np.uint8)
+    for i, r in enumerate(recs):
+        src = (r.pt if op == "seal" else ref_seal(r.slot, r.seq, r.aad, r.pt)) if inputs is None else inputs[i]
+        h_in[in_offs[i]: in_offs[i] + len(src)] = np.frombuffer(src, np.uint8)
+        a = r.aad if aads is None else aads[i]
+        h_aad[aad_offs[i]: aad_offs[i] + len(a)] = np.frombuffer(a, np.uint8)
+    d_in, d_aad = dev(h_in), dev(h_aad)
+    d_out = d_in if in_place else dev(np.full(out_total, FILL, np.uint8))
+    b = ptls_hip.Batch(engine, d)
+    b.set_chacha_lanes(g)
+    assert b.chacha_lanes == (g if g else b.chacha_lanes)
+    res = None
+    if op == "seal":
+        b.chacha_seal(keyset, d_in, d_aad, d_out)
+    else:
+        d_res = torch.full((n,), 7, dtype=torch.int64, device="cuda")
+        b.chacha_open(keyset, d_in, d_aad, d_out, d_res)
+    torch.cuda.synchronize()
+    if op == "open":
+        res = [int(x) & U64 for x in d_res.cpu().numpy().tolist()]
+    b.close()
+    return res, d_out.cpu().numpy(), (h_in if in_place else np.full(out_total, FILL, np.uint8)), out_offs
+
+
+def image(base, offs, pieces):
+    img = base.copy()
+    for o, p in zip(offs, pieces):
+        img[o: o + len(p)] = np.frombuffer(p, np.uint8)
+    return img
+
+
+def check_seal_open(engine, keyset, recs, g, aligned):
+    sealed = [ref_seal(r.slot, r.seq, r.aad, r.pt) for r in recs]
+    for in_place in (False, True):
+        _, out, base, offs = run(engine, keyset, recs, g, aligned, "seal", in_place)
+        assert np.array_equal(out, image(base, offs, sealed)), ("seal", g, aligned, in_place)
+        res, out, base, offs = run(engine, keyset, recs, g, aligned, "open", in_place)
+        assert res == [len(r.pt) for r in recs], ("open result", g, aligned, in_place)
+        assert np.array_equal(out, image(base, offs, [r.pt for r in recs])), ("open", g, aligned, in_place)
+
+
+@pytest.mark.parametrize("aligned", [False, True], ids=["packed", "aligned16"])
+@pytest.mark.parametrize("g", GS)
+def test_length_sweep(engine, keyset, g, aligned):
+    """every length x every AAD length at lanes-per-record g: seal, open and both in place, odd or 16-aligned offsets"""
+    recs = []
+    for li, L in enumerate(lens_of(g)):
+        for A in AADS:
+            recs.append(Rec(li % 4, SEQS[li % 5], AAD[:A], PAYLOAD[:L]))
+    check_seal_open(engine, keyset, recs, g, aligned)
+
+
+@pytest.mark.parametrize("g", [1, 4, 16])
+def test_one_wave_mixed_groups(engine, keyset, g):
+    """groups of one wave with different trip counts: lengths 0, 1, 64 g + 1, 16384 and 5 interleaved, in several orders"""
+    base = [Rec(k % 4, SEQS[k % 5], AAD[:13], PAYLOAD[k: k + L]) for k, L in enumerate([0, 1, 64 * g + 1, 16384, 5] * 4)]
+    for seed in range(3):
+        recs = list(base)
+        if seed:
+            random.Random(seed).shuffle(recs)
+        check_seal_open(engine, keyset, recs, g, seed == 2)
+
+
+def test_sequence_numbers_and_keys(engine, keyset):
+    """300 records over 64 key slots in shuffled order, every sequence-number edge; automatic lanes"""
+    rng = random.Random(300)
+    recs = [Rec(i % NKEYS, SEQS[i % 5], AAD[: rng.choice(AADS)], PAYLOAD[i: i + rng.randrange(0, 600)]) for i in range(300)]
+    rng.shuffle(recs)
+    check_seal_open(engine, keyset, recs, 0, False)
+
+
+def test_key_slot_outside_keyset_is_refused(engine, keyset):
+    d = np.zeros(2, dtype=ptls_hip.RECORD_DTYPE)
+    d["len"], d["out_off"], d["in_off"], d["key"] = [16, 16], [0, 64], [0, 64], [0, NKEYS]
+    b = ptls_hip.Batch(engine, d)
+    d_in = torch.zeros(256, dtype=torch.uint8, device="cuda")
+    d_out = torch.full((256,), FILL, dtype=torch.uint8, device="cuda")
+    rc = ptls_hip.lib().ptls_hip_chacha20poly1305_seal_batch(b.ptr, keyset.ptr, d_in.data_ptr(), d_in.data_ptr(),
+                                                             d_out.data_ptr(), None)
+    torch.cuda.synchronize()
+    assert rc == ptls_hip.EINVAL and bool((d_out == FILL).all())
+    b.close()
+
+
+@pytest.mark.parametrize("g", GS)
+def test_open_failures(engine, keyset, g):
+    """one damaged bit in the ciphertext, the tag, the AAD or the sequence number: UINT64_MAX for exactly those records, the
+    plaintext bytes still written, the neighbours in the same wave untouched"""
+    lens = [0, 1, 100, 1350, 5000, 64 * g + 1, 17, 4096]
+    recs = [Rec(i % 4, SEQS[i % 5], AAD[:13], PAYLOAD[i: i + lens[i % len(lens)]]) for i in range(64)]
+    inputs = [bytearray(ref_seal(r.slot, r.seq, r.aad, r.pt)) for r in recs]
+    aads = [bytearray(r.aad) for r in recs]
+    seqs = [r.seq for r in recs]
+    damaged = {}
+    for i in range(1, 64, 3):
+        kind = ("ct", "tag", "aad", "seq")[(i // 3) % 4]
+        L = len(recs[i].pt)
+        if kind == "ct" and L == 0:
+            kind = "tag"
+        if kind == "ct":
+            inputs[i][(i * 37) % L] ^= 1 << (i % 8)
+        elif kind == "tag":
+            inputs[i][L + i % 16] ^= 0x80
+        elif kind == "aad":
+            aads[i][i % 13] ^= 0x01
+        else:
+            seqs[i] = (seqs[i] + 1) & U64
+        damaged[i] = kind
+    inputs, aads = [bytes(x) for x in inputs], [bytes(x) for x in aads]
+    res, out, base, offs = run(engine, keyset, recs, g, False, "open", inputs=inputs, seqs=seqs, aads=aads)
+    want_pt, want_res = [], []
+    for i, r in enumerate(recs):
+        pt, ok = chacha_ref.open_(KEYS[r.slot], IVS[r.slot], seqs[i], aads[i], inputs[i])
+        assert ok == (i not in damaged)
+        want_pt.append(pt)
+        want_res.append(len(pt) if ok else U64)
+    assert res == want_res
+    assert np.array_equal(out, image(base, offs, want_pt))
+
+
+@pytest.mark.parametrize("g", GS)
+def test_header_protection(engine, fixture, g):
+    """seal_supp and the stand-alone mask call against the fixture's 32 masks (samples inside the ciphertext and over the
+    tag); disabled entries and an hp_key outside the keyset leave their mask bytes untouched"""
+    gold, gen = fixture
+    cases = [gen.mask_inputs(j) for j in range(32)]
+    n = len(cases)
+    ks = ptls_hip.KeySet(engine, 32, n, algo=ptls_hip.ALGO_CHACHA20POLY1305)
+    ks.set(0, b"".join(c[0] for c in cases), b"".join(c[1] for c in cases))
+    hp = ptls_hip.KeySet(engine, 32, n, algo=ptls_hip.ALGO_CHACHA20POLY1305)
+    hp.set(0, b"".join(c[5] for c in cases), None)
+    lens = [len(c[4]) for c in cases]
+    in_offs, in_total = place(lens, False)
+    out_offs, out_total = place([l + 16 for l in lens], False)
+    aad_offs, aad_total = place([len(c[3]) for c in cases], False)
+    mask_offs, mask_total = place([16] * n, False)
+    d = np.zeros(n, dtype=ptls_hip.RECORD_DTYPE)
+    d["in_off"], d["out_off"], d["aad_off"] = in_offs, out_offs, aad_offs
+    d["seq"], d["len"], d["aad_len"], d["key"] = [c[2] for c in cases], lens, [len(c[3]) for c in cases], list(range(n))
+    sp = np.zeros(n, dtype=ptls_hip.SUPP_DTYPE)
+    sp["sample_off"] = [o + c[6] for o, c in zip(out_offs, cases)]
+    sp["mask_off"], sp["hp_key"], sp["flags"] = mask_offs, list(range(n)), ptls_hip.SUPP_ENABLE
+    skipped = {5: "disabled", 11: "hp_key", 20: "disabled", 29: "hp_key"}
+    for i, why in skipped.items():
+        if why == "disabled":
+            sp["flags"][i] = 0
+        else:
+            sp["hp_key"][i] = n + i
+    h_in, h_aad = np.full(in_total, FILL, np.uint8), np.full(aad_total, FILL, np.uint8)
+    for i, c in enumerate(cases):
+        h_in[in_offs[i]: in_offs[i] + lens[i]] = np.frombuffer(c[4], np.uint8)
+        h_aad[aad_offs[i]: aad_offs[i] + len(c[3])] = np.frombuffer(c[3], np.uint8)
+    d_in, d_aad = dev(h_in), dev(h_aad)
+    d_out, d_mask = dev(np.full(out_total, FILL, np.uint8)), dev(np.full(mask_total, FILL, np.uint8))
+    d_sp = dev(np.frombuffer(sp.tobytes(), np.uint8).copy())
+    b = ptls_hip.Batch(engine, d)
+    b.set_chacha_lanes(g)
+    b.chacha_seal_supp(ks, hp, d_sp, d_in, d_aad, d_out, d_mask)
+    torch.cuda.synchronize()
+    out, mask = d_out.cpu().numpy(), d_mask.cpu().numpy()
+    sealed = [chacha_ref.seal(*c[:5]) for c in cases]
+    for c, s, e in zip(cases, sealed, gold["masks"]):
+        assert hashlib.sha256(s).hexdigest() == e["sha256"] and e["sample_off"] == c[6]
+    assert np.array_equal(out, image(np.full(out_total, FILL, np.uint8), out_offs, sealed))
+    want = [bytes.fromhex(e["mask"]) if i not in skipped else bytes([FILL]) * 16 for i, e in enumerate(gold["masks"])]
+    for i, (c, s) in enumerate(zip(cases, sealed)):
+        if i not in skipped:
+            assert want[i] == chacha_ref.hp_mask(c[5], s[c[6]: c[6] + 16])
+    want_img = image(np.full(mask_total, FILL, np.uint8), mask_offs, want)
+    assert np.array_equal(mask, want_img)
+    # the receive side: the same samples, read from the sealed packets
+    d_mask2 = dev(np.full(mask_total, FILL, np.uint8))
+    engine.chacha20_mask(hp, d_sp, d_out, d_mask2)
+    torch.cuda.synchronize()
+    assert np.array_equal(d_mask2.cpu().numpy(), want_img)
+    b.close()
+    ks.close()
+    hp.close()
+
+
+def test_fixture_records(engine, fixture):
+    """the 200 records recorded from picotls's minicrypto engine, sealed in one batch (automatic lanes) and opened again"""
+    gold, gen = fixture
+    cases = [gen.record_inputs(e["i"]) for e in gold["records"]]
+    n = len(cases)
+    ks = ptls_hip.KeySet(engine, 32, n, algo=ptls_hip.ALGO_CHACHA20POLY1305)
+    ks.set(0, b"".join(c[0] for c in cases), b"".join(c[1] for c in cases))
+    lens = [len(c[4]) for c in cases]
+    recs, in_total, out_total, aad_total = ptls_hip.layout_records(lens, [len(c[3]) for c in cases], list(range(n)),
+                                                                   [0] * n, align=16)
+    recs["seq"] = np.array([c[2] for c in cases], dtype=np.uint64)
+    h_in, h_aad = np.zeros(in_total + 16, np.uint8), np.zeros(aad_total + 16, np.uint8)
+    for c, r in zip(cases, recs):
+        h_in[r["in_off"]: r["in_off"] + len(c[4])] = np.frombuffer(c[4], np.uint8)
+        h_aad[r["aad_off"]: r["aad_off"] + len(c[3])] = np.frombuffer(c[3], np.uint8)
+    d_in, d_aad = dev(h_in), dev(h_aad)
+    d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device="cuda")
+    b = ptls_hip.Batch(engine, recs)
+    b.chacha_seal(ks, d_in, d_aad, d_out)
+    d_pt = torch.zeros(out_total + 16, dtype=torch.uint8, device="cuda")
+    d_res = torch.zeros(n, dtype=torch.int64, device="cuda")
+    orecs = recs.copy()
+    orecs["in_off"] = recs["out_off"]  # the sealed records lie where the seal put them
+    ob = ptls_hip.Batch(engine, orecs)
+    ob.chacha_open(ks, d_out, d_aad, d_pt, d_res)
+    torch.cuda.synchronize()
+    ob.close()
+    out, pt = d_out.cpu().numpy(), d_pt.cpu().numpy()
+    for c, r, e in zip(cases, recs, gold["records"]):
+        got = out[r["out_off"]: r["out_off"] + r["len"] + 16].tobytes()
+        assert hashlib.sha256(got).hexdigest() == e["sha256"], e["i"]
+        if "out" in e:
+            assert got.hex() == e["out"], e["i"]
+        assert pt[r["out_off"]: r["out_off"] + r["len"]].tobytes() == c[4]
+    assert d_res.cpu().numpy().tolist() == lens
+    b.close()
+    ks.close()
+
+
+def hkdf_expand_label(secret, label, length):
+    """HKDF-Expand-Label(secret, label, "", length) with SHA-256 (RFC 8446 §7.1), length <= 32"""
+    full = b"tls13 " + label
+    info = struct.pack(">H", length) + bytes([len(full)]) + full + b"\x00"
+    return hmac.new(secret, info + b"\x01", hashlib.sha256).digest()[:length]
+
+
+def test_key_schedule(engine):
+    """set_secrets / update_secrets with hash_size 32 against HKDF-Expand-Label from Python's hmac; records sealed after an
+    update use the new keys"""
+    n = 70
+    secrets = [stream("gpu-chacha-secret-%d" % i, 32) for i in range(n)]
+    ks = ptls_hip.KeySet(engine, 32, n, algo=ptls_hip.ALGO_CHACHA20POLY1305)
+    ks.set_secrets(0, b"".join(secrets), 32)
+    for rounds in range(2):
+        keys = [hkdf_expand_label(s, b"key", 32) for s in secrets]
+        ivs = [hkdf_expand_label(s, b"iv", 12) for s in secrets]
+        assert [ks.get_iv(i) for i in range(n)] == ivs
+        lens = [(i * 29) % 300 for i in range(n)]
+        recs, in_total, out_total, aad_total = ptls_hip.layout_records(lens, [5] * n, list(range(n)), [rounds + 3] * n)
+        h_in = np.frombuffer(stream("gpu-chacha-ks-in", in_total + 16), np.uint8).copy()
+        h_aad = np.frombuffer(stream("gpu-chacha-ks-aad", aad_total + 16), np.uint8).copy()
+        d_out = torch.zeros(out_total + 16, dtype=torch.uint8, device="cuda")
+        b = ptls_hip.Batch(engine, recs)
+        b.chacha_seal(ks, dev(h_in), dev(h_aad), d_out)
+        torch.cuda.synchronize()
+        out = d_out.cpu().numpy()
+        for i, r in enumerate(recs):
+            want = chacha_ref.seal(keys[i], ivs[i], rounds + 3, h_aad[r["aad_off"]: r["aad_off"] + 5].tobytes(),
+                                   h_in[r["in_off"]: r["in_off"] + lens[i]].tobytes())
+            assert out[r["out_off"]: r["out_off"] + lens[i] + 16].tobytes() == want, (rounds, i)
+        b.close()
+        if rounds == 0:
+            nxt = ks.update_secrets(0, b"".join(secrets), 32)
+            secrets = [hkdf_expand_label(s, b"traffic upd", 32) for s in secrets]
+            assert nxt == b"".join(secrets)
+    ks.close()
+
+
+def test_tls13_record_layer(engine, keyset):
+    """tls13_frame + tls13_seal of messages of 0, 1, 16384, 16385 and 40000 bytes: every wire record is header ||
+    ChaCha20-Poly1305(chunk || type, AAD = header); tls13_parse + tls13_open gives the content, lengths and types back; an
+    all-zero inner plaintext is NO_CONTENT_TYPE"""
+    # (63, 127 and 16383 as well: with the content type the record then ends on a whole ChaCha block)
+    sizes, types = [0, 1, 16384, 16385, 40000, 63, 127, 16383], [23, 22, 23, 21, 23, 23, 22, 23]
+    msgs = np.zeros(len(sizes), dtype=ptls_hip.TLS13_MESSAGE_DTYPE)
+    in_off = out_off = 0
+    for i, L in enumerate(sizes):
+        msgs[i] = (in_off, out_off, SEQS[i % 5], L, i, types[i], 0)
+        in_off += L + 3
+        out_off += ptls_hip.lib().ptls_hip_tls13_wire_size(L)
+    recs = ptls_hip.tls13_frame(msgs)
+    h_in = np.frombuffer(stream("gpu-chacha-tls13", in_off + 16), np.uint8).copy()
+    d_wire = torch.full((out_off + 16,), FILL, dtype=torch.uint8, device="cuda")
+    b = ptls_hip.Batch(engine, recs)
+    b.tls13_seal(keyset, dev(h_in), d_wire)
+    torch.cuda.synchronize()
+    wire = d_wire.cpu().numpy().tobytes()
+    b.close()
+    want, contents = b"", []
+    for i, L in enumerate(sizes):
+        payload = h_in[int(msgs[i]["in_off"]): int(msgs[i]["in_off"]) + L].tobytes()
+        for j, o in enumerate(range(0, L, 16384)):
+            chunk = payload[o: o + 16384]
+            hdr = b"\x17\x03\x03" + struct.pack(">H", len(chunk) + 17)
+            want += hdr + ref_seal(i, (SEQS[i % 5] + j) & U64, hdr, chunk + bytes([types[i]]))
+            contents.append((i, (SEQS[i % 5] + j) & U64, types[i], chunk))
+    assert wire == want + bytes([FILL]) * 16
+    # receive side, one connection (key slot) at a time
+    pos = k = 0
+    for i, L in enumerate(sizes):
+        nrec = (L + 16383) // 16384
+        size = ptls_hip.lib().ptls_hip_tls13_wire_size(L)
+        if nrec == 0:
+            continue
+        prs, consumed = ptls_hip.tls13_parse(want[pos: pos + size], wire_off=pos, key=i, seq=SEQS[i % 5], out_base=0)
+        assert consumed == size and len(prs) == nrec
+        d_pt = torch.full((L + 64,), FILL, dtype=torch.uint8, device="cuda")
+        d_res = torch.zeros(nrec, dtype=torch.int64, device="cuda")
+        ob = ptls_hip.Batch(engine, prs)
+        ob.tls13_open(keyset, d_wire, d_pt, d_res)
+        torch.cuda.synchronize()
+        res, pt = [int(x) & U64 for x in d_res.cpu().numpy()], d_pt.cpu().numpy()
+        for r, v in zip(prs, res):
+            _, _, t, chunk = contents[k]
+            assert (v >> 56, v & ((1 << 56) - 1)) == (t, len(chunk))
+            assert pt[int(r["out_off"]): int(r["out_off"]) + len(chunk)].tobytes() == chunk
+            k += 1
+        ob.close()
+        pos += size
+    # an all-zero inner plaintext
+    hdr = b"\x17\x03\x03" + struct.pack(">H", 10 + 16)
+    rec = hdr + ref_seal(2, 9, hdr, bytes(10))
+    prs, consumed = ptls_hip.tls13_parse(rec, key=2, seq=9)
+    assert consumed == len(rec) and len(prs) == 1
+    d_res = torch.zeros(1, dtype=torch.int64, device="cuda")
+    ob = ptls_hip.Batch(engine, prs)
+    ob.tls13_open(keyset, dev(np.frombuffer(rec + bytes(16), np.uint8).copy()), torch.zeros(64, dtype=torch.uint8, device="cuda"),
+                  d_res)
+    torch.cuda.synchronize()
+    assert int(d_res.cpu().numpy()[0]) & U64 == ptls_hip.TLS13_NO_CONTENT_TYPE
+    ob.close()
+
+
+def test_mismatched_calls_are_refused(engine, keyset):
+    """every call that cannot serve the keyset it is given returns PTLS_HIP_EINVAL and launches nothing; a following correct
+    call on the same objects still passes"""
+    L = ptls_hip.lib()
+    aes = ptls_hip.KeySet(engine, 32, 4)
+    aes.set(0, b"".join(KEYS[:4]), b"".join(IVS[:4]))
+    recs, in_total, out_total, aad_total = ptls_hip.layout_records([100, 33], [5, 5], [0, 1], [1, 2])
+    b = ptls_hip.Batch(engine, recs)
+    d_in = dev(np.frombuffer(PAYLOAD[: in_total + 16], np.uint8).copy())
+    d_aad = dev(np.frombuffer(AAD[: aad_total + 16], np.uint8).copy())
+    d_out = torch.full((out_total + 16,), FILL, dtype=torch.uint8, device="cuda")
+    d_mask = torch.full((64,), FILL, dtype=torch.uint8, device="cuda")
+    d_res = torch.full((2,), 7, dtype=torch.int64, device="cuda")
+    sp = np.zeros(2, dtype=ptls_hip.SUPP_DTYPE)
+    sp["mask_off"], sp["flags"] = [0, 16], ptls_hip.SUPP_ENABLE
+    d_sp = dev(np.frombuffer(sp.tobytes(), np.uint8).copy())
+    p = lambda t: t.data_ptr()  # noqa: E731
+    calls = [
+        L.ptls_hip_aesgcm_seal_batch(b.ptr, keyset.ptr, p(d_in), p(d_aad), p(d_out), None),
+        L.ptls_hip_aesgcm_open_batch(b.ptr, keyset.ptr, p(d_in), p(d_aad), p(d_out), p(d_res), None),
+        L.ptls_hip_aesgcm_seal_batch_supp(b.ptr, keyset.ptr, keyset.ptr, p(d_sp), p(d_in), p(d_aad), p(d_out), p(d_mask), None),
+        L.ptls_hip_aesgcm_seal_batch_supp(b.ptr, aes.ptr, keyset.ptr, p(d_sp), p(d_in), p(d_aad), p(d_out), p(d_mask), None),
+        L.ptls_hip_aesecb_batch(engine.ptr, keyset.ptr, p(d_sp), 2, p(d_out), p(d_mask), None),
+        L.ptls_hip_chacha20poly1305_seal_batch(b.ptr, aes.ptr, p(d_in), p(d_aad), p(d_out), None),
+        L.ptls_hip_chacha20poly1305_open_batch(b.ptr, aes.ptr, p(d_in), p(d_aad), p(d_out), p(d_res), None),
+        L.ptls_hip_chacha20poly1305_seal_batch_supp(b.ptr, keyset.ptr, aes.ptr, p(d_sp), p(d_in), p(d_aad), p(d_out), p(d_mask),
+                                                    None),
+        L.ptls_hip_chacha20poly1305_seal_batch_supp(b.ptr, aes.ptr, aes.ptr, p(d_sp), p(d_in), p(d_aad), p(d_out), p(d_mask),
+                                                    None),
+        L.ptls_hip_chacha20_mask_batch(engine.ptr, aes.ptr, p(d_sp), 2, p(d_out), p(d_mask), None),
+    ]
+    # the host pipelines serve AES-GCM keysets only
+    pipe = ptls_hip.Pipeline(engine, 1 << 20)
+    h_in, h_out = np.zeros(in_total + 16, np.uint8), np.full(out_total + 16, FILL, np.uint8)
+    h_aad, h_res, h_mask = np.zeros(aad_total + 16, np.uint8), np.zeros(2, np.uint64), np.full(64, FILL, np.uint8)
+    q = lambda a: a.ctypes.data  # noqa: E731
+    calls += [
+        L.ptls_hip_pipeline_seal(pipe.ptr, keyset.ptr, q(recs), 2, q(h_in), q(h_aad), q(h_out)),
+        L.ptls_hip_pipeline_open(pipe.ptr, keyset.ptr, q(recs), 2, q(h_in), q(h_aad), q(h_out), q(h_res)),
+        L.ptls_hip_pipeline_seal_supp(pipe.ptr, keyset.ptr, keyset.ptr, q(recs), q(sp), 2, q(h_in), q(h_aad), q(h_out), q(h_mask)),
+        L.ptls_hip_pipeline_seal_supp(pipe.ptr, aes.ptr, keyset.ptr, q(recs), q(sp), 2, q(h_in), q(h_aad), q(h_out), q(h_mask)),
+        L.ptls_hip_pipeline_tls13_seal(pipe.ptr, keyset.ptr, q(recs), 2, q(h_in), q(h_out)),
+        L.ptls_hip_pipeline_tls13_open(pipe.ptr, keyset.ptr, q(recs), 2, q(h_in), q(h_out), q(h_res)),
+    ]
+    torch.cuda.synchronize()
+    assert calls == [ptls_hip.EINVAL] * len(calls)
+    assert bool((d_out == FILL).all()) and bool((d_mask == FILL).all()) and bool((d_res == 7).all())
+    assert bool((h_out == FILL).all()) and bool((h_mask == FILL).all())
+    pipe.close()
+    # the same objects, used as they are meant to be
+    b.chacha_seal(keyset, d_in, d_aad, d_out)
+    torch.cuda.synchronize()
+    out = d_out.cpu().numpy()
+    for i, r in enumerate(recs):
+        want = ref_seal(i, int(r["seq"]), AAD[int(r["aad_off"]): int(r["aad_off"]) + 5],
+                        PAYLOAD[int(r["in_off"]): int(r["in_off"]) + int(r["len"])])
+        assert out[int(r["out_off"]): int(r["out_off"]) + int(r["len"]) + 16].tobytes() == want
+    b.seal(aes, d_in, d_aad, d_out)
+    torch.cuda.synchronize()
+    b.close()
+    aes.close()
+
+
+_PLUGIN_CASE = r"""
+import ctypes as c, hashlib, importlib.util, json, os, sys
+sys.path[:0] = {paths!r}
+import ptls_hip, chacha_ref
+import plugin_driver as pd
+from oracle_lib import REF_SO
+root = {root!r}
+spec = importlib.util.spec_from_file_location("g", os.path.join(root, "tests", "golden", "make_chacha_golden.py"))
+gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
+gold = json.load(open(os.path.join(root, "tests", "golden", "chacha20poly1305.json")))
+hip, ref = ptls_hip.lib(), c.CDLL(REF_SO)
+ref.ptls_aead_new_direct.restype = c.c_void_p
+ref.ptls_aead_new_direct.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
+ref.ptls_aead_free.argtypes = [c.c_void_p]
+ref.ptls_cipher_new.restype = c.c_void_p
+ref.ptls_cipher_new.argtypes = [c.c_void_p, c.c_int, c.c_void_p]
+ref.ptls_cipher_free.argtypes = [c.c_void_p]
+aead = c.addressof(c.c_char.in_dll(hip, "ptls_hip_chacha20poly1305"))
+cipher = c.addressof(c.c_char.in_dll(hip, "ptls_hip_chacha20"))
+drv = pd.PluginDriver.__new__(pd.PluginDriver)  # the vtable dispatchers only: its __init__ binds the AES objects
+calls = 0
+# the fixture's records of the plugin lengths, through ptls_aead_new_direct / ptls_aead_encrypt / ptls_aead_decrypt
+want_lens = {{0, 1, 63, 64, 65, 1500, 16384}}
+for e in gold["records"]:
+    if e["L"] not in want_lens:
+        continue
+    key, iv, seq, aad, pt = gen.record_inputs(e["i"])
+    enc, dec = ref.ptls_aead_new_direct(aead, 1, key, iv), ref.ptls_aead_new_direct(aead, 0, key, iv)
+    assert enc and dec, ptls_hip.last_error()
+    out = drv.encrypt(enc, pt, seq, aad)
+    assert hashlib.sha256(out).hexdigest() == e["sha256"] and out.hex() == e.get("out", out.hex()), ("encrypt", e["i"])
+    assert drv.decrypt(dec, out, seq, aad) == pt, ("decrypt", e["i"])
+    bad = bytearray(out); bad[-1] ^= 1
+    assert drv.decrypt(dec, bytes(bad), seq, aad) is None, ("bad tag", e["i"])
+    parts = [pt[: len(pt) // 3], pt[len(pt) // 3:]]
+    assert drv.encrypt_v(enc, parts, seq, aad) == out, ("encrypt_v", e["i"])
+    ref.ptls_aead_free(enc); ref.ptls_aead_free(dec)
+    calls += 1
+assert calls >= 7 * 2, calls
+key, iv, seq, aad, pt = gen.record_inputs(7)
+pt, seq, aad = (pt * 1500)[:1500] or bytes(1500), (1 << 64) - 1, b"\x17\x03\x03\x05\xec"
+enc = ref.ptls_aead_new_direct(aead, 1, key, iv)
+assert drv.encrypt(enc, pt, seq, aad) == chacha_ref.seal(key, iv, seq, aad, pt)
+# IV-only re-setup (key NULL) through the algorithm's setup_crypto: the context then seals under the new IV
+class Algo(c.Structure):
+    _fields_ = [("name", c.c_char_p), ("conf", c.c_uint64), ("integ", c.c_uint64), ("ctr", c.c_void_p), ("ecb", c.c_void_p),
+                ("key_size", c.c_size_t), ("iv_size", c.c_size_t), ("tag_size", c.c_size_t), ("fixed_iv", c.c_size_t),
+                ("record_iv", c.c_size_t), ("nt_and_align_bits", c.c_uint64), ("context_size", c.c_size_t),
+                ("setup", c.c_void_p)]
+setup = c.CFUNCTYPE(c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p)(Algo.from_address(aead).setup)
+iv2 = bytes(b ^ 0x5a for b in iv)
+assert setup(enc, 1, None, iv2) == 0
+assert drv.encrypt(enc, pt, 5, aad) == chacha_ref.seal(key, iv2, 5, aad, pt)
+ref.ptls_aead_free(enc)
+# supp with a ptls_hip_chacha20 context: the fixture's masks (ptls_aead_encrypt_s), and the cipher on its own
+for e in gold["masks"]:
+    key, iv, seq, aad, pt, hp_key, sample_off = gen.mask_inputs(e["j"])
+    enc, hp = ref.ptls_aead_new_direct(aead, 1, key, iv), ref.ptls_cipher_new(cipher, 1, hp_key)
+    assert enc and hp, ptls_hip.last_error()
+    out, mask = drv.encrypt_s(enc, pt, seq, aad, hp, sample_off)
+    assert hashlib.sha256(out).hexdigest() == e["sha256"] and mask.hex() == e["mask"], ("supp", e["j"])
+    assert drv.cipher_encrypt(hp, out[sample_off: sample_off + 16], bytes(5)) == mask[:5], ("cipher", e["j"])
+    ref.ptls_cipher_free(hp); ref.ptls_aead_free(enc)
+    calls += 1
+print("ok", calls)
+"""
+
+
+@pytest.mark.parametrize("worker", ["1", "0"])
+def test_plugin_objects(worker):
+    """ptls_hip_chacha20poly1305 / ptls_hip_chacha20 under the reference's own ptls_aead_new_direct, ptls_aead_encrypt,
+    ptls_aead_encrypt_s and ptls_aead_decrypt, in a fresh process, whatever PTLS_HIP_PLUGIN_WORKER says"""
+    from oracle_lib import Ref
+    assert Ref.available, "oracle/_ref is not built: __graft_entry__.build() makes it where the reference checkout is present"
+    paths = [os.path.join(ROOT, "tests"), os.path.join(ROOT, "hsig-picotls_amd"), ROOT]
+    env = dict(os.environ, PTLS_HIP_PLUGIN_WORKER=worker)
+    r = subprocess.run([sys.executable, "-c", _PLUGIN_CASE.format(paths=paths, root=ROOT)], env=env, capture_output=True,
+                       text=True, timeout=240)
+    assert r.returncode == 0 and r.stdout.strip().startswith("ok"), (r.returncode, r.stdout[-2000:], r.stderr[-3000:])
