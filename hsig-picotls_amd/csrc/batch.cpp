@@ -169,39 +169,7 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
                     ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305 ? "ChaCha20-Poly1305" : "AES-GCM");
     if (supp != nullptr && hp_ks != nullptr && hp_ks->algo != ks->algo)
         return fail(PTLS_HIP_EINVAL, "seal_batch_supp: the header-protection keyset is of the other algorithm");
-    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
-        if (supp != nullptr && (hp_ks == nullptr || hp_ks->eng != b->eng || mask == nullptr))
-            return fail(PTLS_HIP_EINVAL, "seal_batch_supp: the header-protection keyset must be on the same engine, and mask "
-                                         "must be given");
-        if (b->n == 0)
-            return 0;
-        if (b->max_key >= ks->nslots)
-            return fail(PTLS_HIP_EINVAL, "seal/open: a record names key slot %u, the keyset has %zu", b->max_key, ks->nslots);
-        if (in == nullptr || out == nullptr || (open && result == nullptr))
-            return fail(PTLS_HIP_EINVAL, "seal/open: null buffer");
-        DeviceGuard g(b->eng->device);
-        ChaChaArgs a{};
-        a.recs = b->d_recs; /* descriptor order: no key runs, no chunks */
-        a.n = b->n;
-        a.in = static_cast<const uint8_t *>(in);
-        a.aad = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
-        a.out = static_cast<uint8_t *>(out);
-        a.result = result;
-        a.slots = ks->d_chacha;
-        a.supp = supp;
-        a.hp_slots = hp_ks != nullptr ? hp_ks->d_chacha : nullptr;
-        a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
-        a.mask = static_cast<uint8_t *>(mask);
-        const bool base_aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(a.aad) |
-                                    reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-        const int e = launch_chacha_batch(b->chacha_lanes, open, stream, a, base_aligned && b->all_aligned);
-        if (e != 0)
-            return fail(PTLS_HIP_ELAUNCH, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-        keyset_note_use(ks, stream);
-        keyset_note_use(hp_ks, stream);
-        b->uses.note(stream);
-        return 0;
-    }
+    /* (the key sizes of two ChaCha keysets always agree: 32 bytes) */
     if (supp != nullptr && (hp_ks == nullptr || hp_ks->eng != b->eng || hp_ks->key_size != ks->key_size || mask == nullptr))
         return fail(PTLS_HIP_EINVAL, "seal_batch_supp: the header-protection keyset must be on the same engine with the "
                                      "AEAD's key size, and mask must be given");
@@ -212,34 +180,51 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
     if (in == nullptr || out == nullptr || (open && result == nullptr))
         return fail(PTLS_HIP_EINVAL, "seal/open: null buffer");
     DeviceGuard g(b->eng->device);
-    KernelArgs a{};
-    a.recs = b->d_recs;
-    a.recs_ord = b->d_recs_ord != nullptr ? b->d_recs_ord : b->d_recs;
-    a.order = b->d_order;
-    a.chunks = b->d_chunks;
-    a.nchunks = b->nchunks;
-    a.in = static_cast<const uint8_t *>(in);
-    a.aad = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
-    a.out = static_cast<uint8_t *>(out);
-    a.result = result;
-    a.slots = ks->d_slots;
-    a.basis = ks->d_basis;
-    a.t0 = b->eng->d_t0;
-    a.supp = supp;
-    a.hp_slots = hp_ks != nullptr ? hp_ks->d_slots : nullptr;
-    a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
-    a.mask = static_cast<uint8_t *>(mask);
-    const bool base_aligned = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(a.aad) |
-                                reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    const bool aligned = base_aligned && b->all_aligned;
-    const unsigned grid = plan_grid(b->n, b->nchunks, b->lanes, batch_cus(b));
-    if (b->d_clk != nullptr && b->clk_bytes < (size_t)grid * 32)
-        return fail(PTLS_HIP_EINVAL, "seal/open: the clock-stamp buffer is smaller than 32 bytes x %u workgroups", grid);
-    a.clk = b->d_clk;
-    a.clk_bytes = b->clk_bytes;
-    a.queue = queue_slot(b->eng);
-    const int rounds = ks->key_size == 16 ? 10 : 14;
-    int e = launch_batch(b->lanes, rounds, open, b->wg, grid, stream, a, aligned);
+    const uint8_t *in8 = static_cast<const uint8_t *>(in), *aad8 = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
+    const uint32_t hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
+    const bool aligned = b->all_aligned && ((reinterpret_cast<uintptr_t>(in8) | reinterpret_cast<uintptr_t>(aad8) |
+                                             reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    int e;
+    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
+        ChaChaArgs a{};
+        a.recs = b->d_recs; /* descriptor order: no key runs, no chunks */
+        a.n = b->n;
+        a.in = in8;
+        a.aad = aad8;
+        a.out = static_cast<uint8_t *>(out);
+        a.result = result;
+        a.slots = ks->d_chacha;
+        a.supp = supp;
+        a.hp_slots = hp_ks != nullptr ? hp_ks->d_chacha : nullptr;
+        a.hp_nslots = hp_nslots;
+        a.mask = static_cast<uint8_t *>(mask);
+        e = launch_chacha_batch(b->chacha_lanes, open, stream, a, aligned);
+    } else {
+        KernelArgs a{};
+        a.recs = b->d_recs;
+        a.recs_ord = b->d_recs_ord != nullptr ? b->d_recs_ord : b->d_recs;
+        a.order = b->d_order;
+        a.chunks = b->d_chunks;
+        a.nchunks = b->nchunks;
+        a.in = in8;
+        a.aad = aad8;
+        a.out = static_cast<uint8_t *>(out);
+        a.result = result;
+        a.slots = ks->d_slots;
+        a.basis = ks->d_basis;
+        a.t0 = b->eng->d_t0;
+        a.supp = supp;
+        a.hp_slots = hp_ks != nullptr ? hp_ks->d_slots : nullptr;
+        a.hp_nslots = hp_nslots;
+        a.mask = static_cast<uint8_t *>(mask);
+        const unsigned grid = plan_grid(b->n, b->nchunks, b->lanes, batch_cus(b));
+        if (b->d_clk != nullptr && b->clk_bytes < (size_t)grid * 32)
+            return fail(PTLS_HIP_EINVAL, "seal/open: the clock-stamp buffer is smaller than 32 bytes x %u workgroups", grid);
+        a.clk = b->d_clk;
+        a.clk_bytes = b->clk_bytes;
+        a.queue = queue_slot(b->eng);
+        e = launch_batch(b->lanes, ks->key_size == 16 ? 10 : 14, open, b->wg, grid, stream, a, aligned);
+    }
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     keyset_note_use(ks, stream);
@@ -290,22 +275,34 @@ extern "C" int ptls_hip_chacha20poly1305_seal_batch_supp(ptls_hip_batch_t *b, pt
     return run_batch(b, ks, in, aad, out, nullptr, stream, false, hp_ks, supp, mask, PTLS_HIP_ALGO_CHACHA20POLY1305);
 }
 
-extern "C" int ptls_hip_chacha20_mask_batch(ptls_hip_engine_t *eng, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
-                                            const void *src, void *mask, void *stream)
+/* the stand-alone header-protection masks of n samples (the receive side): one AES-ECB block, or the first 16 ChaCha20
+ * keystream bytes, per sample, with a keyset of `algo`; `who` is the exported call's name in the messages */
+static int mask_batch(const char *who, int algo, ptls_hip_engine_t *eng, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp,
+                      size_t n, const void *src, void *mask, void *stream)
 {
-    if (eng == nullptr || hp_ks == nullptr || hp_ks->eng != eng || hp_ks->algo != PTLS_HIP_ALGO_CHACHA20POLY1305 ||
-        n > 0xffffffffu || (n != 0 && (supp == nullptr || src == nullptr || mask == nullptr)))
-        return fail(PTLS_HIP_EINVAL, "chacha20_mask_batch: bad arguments (a ChaCha keyset of this engine is needed)");
+    const bool chacha = algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
+    if (eng == nullptr || hp_ks == nullptr || hp_ks->eng != eng || hp_ks->algo != algo || n > 0xffffffffu ||
+        (n != 0 && (supp == nullptr || src == nullptr || mask == nullptr)))
+        return fail(PTLS_HIP_EINVAL, "%s: bad arguments (%s keyset of this engine is needed)", who, chacha ? "a ChaCha" : "an AES");
     if (n == 0)
         return 0;
     DeviceGuard g(eng->device);
     const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)eng->ncu * 4);
-    const int e = launch_chacha_mask(supp, (uint32_t)n, static_cast<const uint8_t *>(src), static_cast<uint8_t *>(mask),
-                                     hp_ks->d_chacha, (uint32_t)hp_ks->nslots, grid, stream);
+    const uint8_t *src8 = static_cast<const uint8_t *>(src);
+    uint8_t *mask8 = static_cast<uint8_t *>(mask);
+    const int e = chacha ? launch_chacha_mask(supp, (uint32_t)n, src8, mask8, hp_ks->d_chacha, (uint32_t)hp_ks->nslots, grid, stream)
+                         : launch_aesecb(hp_ks->key_size == 16 ? 10 : 14, supp, (uint32_t)n, src8, mask8, hp_ks->d_slots,
+                                         (uint32_t)hp_ks->nslots, eng->d_t0, grid, stream);
     if (e != 0)
-        return fail(PTLS_HIP_ELAUNCH, "chacha20_mask_batch: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
     keyset_note_use(hp_ks, stream);
     return 0;
+}
+
+extern "C" int ptls_hip_chacha20_mask_batch(ptls_hip_engine_t *eng, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
+                                            const void *src, void *mask, void *stream)
+{
+    return mask_batch("chacha20_mask_batch", PTLS_HIP_ALGO_CHACHA20POLY1305, eng, hp_ks, supp, n, src, mask, stream);
 }
 
 extern "C" int ptls_hip_aesgcm_seal_batch_supp(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
@@ -320,20 +317,7 @@ extern "C" int ptls_hip_aesgcm_seal_batch_supp(ptls_hip_batch_t *b, ptls_hip_key
 extern "C" int ptls_hip_aesecb_batch(ptls_hip_engine_t *eng, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, size_t n,
                                      const void *src, void *mask, void *stream)
 {
-    if (eng == nullptr || hp_ks == nullptr || hp_ks->eng != eng || hp_ks->algo != PTLS_HIP_ALGO_AESGCM || n > 0xffffffffu ||
-        (n != 0 && (supp == nullptr || src == nullptr || mask == nullptr)))
-        return fail(PTLS_HIP_EINVAL, "aesecb_batch: bad arguments");
-    if (n == 0)
-        return 0;
-    DeviceGuard g(eng->device);
-    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)eng->ncu * 4);
-    const int e = launch_aesecb(hp_ks->key_size == 16 ? 10 : 14, supp, (uint32_t)n, static_cast<const uint8_t *>(src),
-                                static_cast<uint8_t *>(mask), hp_ks->d_slots, (uint32_t)hp_ks->nslots, eng->d_t0, grid,
-                                stream);
-    if (e != 0)
-        return fail(PTLS_HIP_ELAUNCH, "aesecb_batch: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    keyset_note_use(hp_ks, stream);
-    return 0;
+    return mask_batch("aesecb_batch", PTLS_HIP_ALGO_AESGCM, eng, hp_ks, supp, n, src, mask, stream);
 }
 
 extern "C" int ptls_hip_aesgcm_open_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out,

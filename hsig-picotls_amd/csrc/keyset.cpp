@@ -11,65 +11,55 @@
 #include <cstring>
 
 #include "host.h"
+
 /* ---------------------------------------------------------------------------------------------- */
 /* keysets                                                                                         */
 /* ---------------------------------------------------------------------------------------------- */
 
-
-
-extern "C" ptls_hip_keyset_t *ptls_hip_keyset_new(ptls_hip_engine_t *eng, size_t key_size, size_t nslots)
+/* The allocator behind both constructors (`who` names the caller in the messages).  AES-GCM: a KeySlot and a GHASH basis per
+ * slot, 16- or 32-byte keys.  ChaCha20-Poly1305: 44 bytes per slot (key + static IV) in its own device array, 32-byte keys.
+ * The key size and the slot count are checked before the engine is touched. */
+static ptls_hip_keyset_t *keyset_alloc(const char *who, ptls_hip_engine_t *eng, int algo, size_t key_size, size_t nslots)
 {
-    if (eng == nullptr || (key_size != 16 && key_size != 32) || nslots == 0 || nslots > 0xffffffffu) {
-        fail(PTLS_HIP_EINVAL, "keyset_new: bad arguments (key_size %zu, nslots %zu)", key_size, nslots);
+    const bool chacha = algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
+    const bool key_ok = chacha ? key_size == 32 : algo == PTLS_HIP_ALGO_AESGCM && (key_size == 16 || key_size == 32);
+    if (eng == nullptr || !key_ok || nslots == 0 || nslots > 0xffffffffu) {
+        fail(PTLS_HIP_EINVAL, "%s: bad arguments (algo %d, key_size %zu, nslots %zu)", who, algo, key_size, nslots);
         return nullptr;
     }
     DeviceGuard g(eng->device);
-    auto *ks = new st_ptls_hip_keyset_t();
+    auto *ks = new st_ptls_hip_keyset_t(); /* every slot array starts null */
     ks->eng = eng;
+    ks->algo = algo;
     ks->key_size = key_size;
     ks->nslots = nslots;
     ks->ivs.assign(nslots * 12, 0);
-    if (dev_alloc(eng, reinterpret_cast<void **>(&ks->d_slots), nslots * sizeof(KeySlot)) != hipSuccess ||
-        dev_alloc(eng, reinterpret_cast<void **>(&ks->d_basis), nslots * BASIS_WORDS_PER_SLOT * 4) != hipSuccess) {
-        fail(PTLS_HIP_ENOMEM, "keyset_new: cannot allocate %zu key slots", nslots);
+    const bool ok = chacha ? dev_alloc(eng, reinterpret_cast<void **>(&ks->d_chacha), nslots * sizeof(ChaChaSlot)) == hipSuccess
+                           : dev_alloc(eng, reinterpret_cast<void **>(&ks->d_slots), nslots * sizeof(KeySlot)) == hipSuccess &&
+                                 dev_alloc(eng, reinterpret_cast<void **>(&ks->d_basis), nslots * BASIS_WORDS_PER_SLOT * 4) == hipSuccess;
+    if (!ok) {
+        fail(PTLS_HIP_ENOMEM, "%s: cannot allocate %zu key slots", who, nslots);
         dev_free(eng, ks->d_slots);
         dev_free(eng, ks->d_basis);
         delete ks;
         return nullptr;
     }
-    (void)hipMemsetAsync(ks->d_slots, 0, nslots * sizeof(KeySlot), eng->util);
+    if (chacha)
+        (void)hipMemsetAsync(ks->d_chacha, 0, nslots * sizeof(ChaChaSlot), eng->util);
+    else
+        (void)hipMemsetAsync(ks->d_slots, 0, nslots * sizeof(KeySlot), eng->util);
     (void)hipStreamSynchronize(eng->util);
     return ks;
 }
 
+extern "C" ptls_hip_keyset_t *ptls_hip_keyset_new(ptls_hip_engine_t *eng, size_t key_size, size_t nslots)
+{
+    return keyset_alloc("keyset_new", eng, PTLS_HIP_ALGO_AESGCM, key_size, nslots);
+}
 
-
-/* A ChaCha20-Poly1305 keyset: 44 bytes per slot (key + static IV) in its own device array; no KeySlot, no GHASH basis. */
 extern "C" ptls_hip_keyset_t *ptls_hip_keyset_new_algo(ptls_hip_engine_t *eng, int algo, size_t key_size, size_t nslots)
 {
-    if (algo == PTLS_HIP_ALGO_AESGCM)
-        return ptls_hip_keyset_new(eng, key_size, nslots);
-    if (eng == nullptr || algo != PTLS_HIP_ALGO_CHACHA20POLY1305 || key_size != 32 || nslots == 0 || nslots > 0xffffffffu) {
-        fail(PTLS_HIP_EINVAL, "keyset_new_algo: bad arguments (algo %d, key_size %zu, nslots %zu)", algo, key_size, nslots);
-        return nullptr;
-    }
-    DeviceGuard g(eng->device);
-    auto *ks = new st_ptls_hip_keyset_t();
-    ks->eng = eng;
-    ks->algo = PTLS_HIP_ALGO_CHACHA20POLY1305;
-    ks->key_size = key_size;
-    ks->nslots = nslots;
-    ks->d_slots = nullptr;
-    ks->d_basis = nullptr;
-    ks->ivs.assign(nslots * 12, 0);
-    if (dev_alloc(eng, reinterpret_cast<void **>(&ks->d_chacha), nslots * sizeof(ChaChaSlot)) != hipSuccess) {
-        fail(PTLS_HIP_ENOMEM, "keyset_new_algo: cannot allocate %zu key slots", nslots);
-        delete ks;
-        return nullptr;
-    }
-    (void)hipMemsetAsync(ks->d_chacha, 0, nslots * sizeof(ChaChaSlot), eng->util);
-    (void)hipStreamSynchronize(eng->util);
-    return ks;
+    return keyset_alloc("keyset_new_algo", eng, algo, key_size, nslots);
 }
 
 extern "C" int ptls_hip_keyset_algo(ptls_hip_keyset_t *ks)
@@ -82,17 +72,7 @@ extern "C" void ptls_hip_keyset_free(ptls_hip_keyset_t *ks)
     if (ks == nullptr)
         return;
     DeviceGuard g(ks->eng->device);
-    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
-        ks->uses.wait();
-        ptls_hip_engine_t *e = ks->eng;
-        (void)hipMemsetAsync(ks->d_chacha, 0, ks->nslots * sizeof(ChaChaSlot), e->util); /* zeroize before release */
-        dev_free(e, ks->d_chacha);
-        (void)hipStreamSynchronize(e->util);
-        std::fill(ks->ivs.begin(), ks->ivs.end(), 0);
-        delete ks;
-        return;
-    }
-    if (ks->pool_id >= 0) { /* a plugin context's pooled slot: zeroed and retired, nothing waits */
+    if (ks->pool_id >= 0) { /* a plugin context's pooled slot (AES only): zeroed and retired, nothing waits */
         pool_release(ks);
         std::fill(ks->ivs.begin(), ks->ivs.end(), 0);
         delete ks;
@@ -104,8 +84,13 @@ extern "C" void ptls_hip_keyset_free(ptls_hip_keyset_t *ks)
     /* zeroize key material before release (ptls_clear_memory in aesgcm_dispose_crypto, lib/fusion.c:1102-1107, :1042-1048),
      * then release in the same stream order */
     ptls_hip_engine_t *e = ks->eng;
-    (void)hipMemsetAsync(ks->d_slots, 0, ks->nslots * sizeof(KeySlot), e->util);
-    (void)hipMemsetAsync(ks->d_basis, 0, ks->nslots * BASIS_WORDS_PER_SLOT * 4, e->util);
+    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
+        (void)hipMemsetAsync(ks->d_chacha, 0, ks->nslots * sizeof(ChaChaSlot), e->util);
+    } else {
+        (void)hipMemsetAsync(ks->d_slots, 0, ks->nslots * sizeof(KeySlot), e->util);
+        (void)hipMemsetAsync(ks->d_basis, 0, ks->nslots * BASIS_WORDS_PER_SLOT * 4, e->util);
+    }
+    dev_free(e, ks->d_chacha); /* the arrays of the other algorithm are null */
     dev_free(e, ks->d_slots);
     dev_free(e, ks->d_basis);
     (void)hipStreamSynchronize(e->util);

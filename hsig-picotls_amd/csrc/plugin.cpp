@@ -1,8 +1,11 @@
 /*
  * plugin.cpp -- the picotls plugin objects: ptls_hip_aes{128,256}gcm and the non-temporal variants
  * (ptls_aead_algorithm_t, lib/fusion.c:1102-1256, :2109-2179), ptls_hip_aes{128,256}ctr (:1050-1100), fusion's one-block
- * ECB API (:857-928) and its low-level single-record context (include/picotls/fusion.h:56-96).  Each call runs one record
- * through the resident worker (plugin_worker.cpp) or its own launch.
+ * ECB API (:857-928) and its low-level single-record context (include/picotls/fusion.h:56-96), and ptls_hip_chacha20poly1305 /
+ * ptls_hip_chacha20 (ptls_minicrypto_chacha20poly1305 / _chacha20, lib/cifra/chacha20.c:44-113).  Each call runs one record
+ * through the resident worker (plugin_worker.cpp; AES only) or its own launch.  The AEAD objects share one vtable, one set-up
+ * routine and one launched-call skeleton, the cipher objects one state; the ciphers part where the keyset is made
+ * (pool_keyset / chacha_keyset), where the kernel is launched (launch_aes / launch_chacha) and at do_init.
  */
 #include <algorithm>
 #include <cstdarg>
@@ -92,17 +95,36 @@ static void plugin_wait(hipStream_t stream, const uint8_t *word_p, uint32_t seq)
     }
 }
 
+/* how an object's one-slot keyset is made: pool_keyset (AES: a slot of the plugin's pool, plugin_worker.cpp) or
+ * chacha_keyset.  iv == nullptr: a header-protection key */
+typedef ptls_hip_keyset_t *(*keyset_maker)(ptls_hip_engine_t *eng, size_t key_size, const void *key, const void *iv);
 
-/* ---- CTR cipher for header protection (replaces lib/fusion.c:1050-1100) ---------------------------- */
+/* a one-slot ChaCha keyset of its own (44 bytes of device memory; the plugin's slot pool holds AES slots) */
+static ptls_hip_keyset_t *chacha_keyset(ptls_hip_engine_t *eng, size_t key_size, const void *key, const void *iv)
+{
+    ptls_hip_keyset_t *ks = ptls_hip_keyset_new_algo(eng, PTLS_HIP_ALGO_CHACHA20POLY1305, key_size, 1);
+    if (ks == nullptr)
+        return nullptr;
+    hipStream_t stream = pool_stream();
+    const int rc = ptls_hip_keyset_set(ks, 0, 1, key, iv, stream);
+    pool_stream_put(stream);
+    if (rc != 0) {
+        ptls_hip_keyset_free(ks);
+        return nullptr;
+    }
+    return ks;
+}
+
+/* ---- CTR / ChaCha20 cipher for header protection (replaces lib/fusion.c:1050-1100, lib/cifra/chacha20.c:44-62) ---- */
 
 struct hip_ctr_state {
     ptls_hip_engine_t *eng;
-    ptls_hip_keyset_t *ks; /* pooled slot */
-    uint8_t *h_stage; /* pooled 256-B pinned piece: [output block @48][completion word @64] */
+    ptls_hip_keyset_t *ks; /* AES: pooled slot; ChaCha20: a one-slot keyset of its own */
+    uint8_t *h_stage; /* pooled 256-B pinned piece.  AES: [output block @48][completion word @64]; ChaCha20: CC_* */
     uint8_t *d_stage; /* its device address: the kernel reads and writes it in place */
     uint8_t bits[16];
     bool ready;
-    uint32_t done_seq; /* completion word sequence of the last block (ECB_DONE) */
+    uint32_t done_seq; /* completion word sequence of the last block (ECB_DONE; AES) */
 };
 
 struct hip_ctr_context {
@@ -110,11 +132,12 @@ struct hip_ctr_context {
     hip_ctr_state *st;
 };
 
-extern "C" ptls_cipher_algorithm_t ptls_hip_aes128ctr, ptls_hip_aes256ctr;
+extern "C" ptls_cipher_algorithm_t ptls_hip_aes128ctr, ptls_hip_aes256ctr, ptls_hip_chacha20;
 
+/* the state of one of this library's cipher contexts, or nullptr */
 static const hip_ctr_state *ctr_state_of(const ptls_cipher_context_t *c)
 {
-    if (c == nullptr || (c->algo != &ptls_hip_aes128ctr && c->algo != &ptls_hip_aes256ctr))
+    if (c == nullptr || (c->algo != &ptls_hip_aes128ctr && c->algo != &ptls_hip_aes256ctr && c->algo != &ptls_hip_chacha20))
         return nullptr;
     return reinterpret_cast<const hip_ctr_context *>(c)->st;
 }
@@ -161,8 +184,8 @@ static void ecb_block(hip_ctr_state *st, const void *src, uint8_t dst[16])
         w.mbox[j].mu.unlock();
         return;
     }
-    /* one launch per block (worker off, or PTLS_HIP_ECB_LAUNCH=1): the block travels in the kernel arguments */
-    /* the block goes in the kernel arguments; the result comes back through the pinned staging (@48) */
+    /* one launch per block (worker off, or PTLS_HIP_ECB_LAUNCH=1): the block travels in the kernel arguments, the result
+     * comes back through the pinned staging (@48) */
     hipStream_t stream = pool_stream();
     const int e = launch_aesecb_one(st->ks->key_size == 16 ? 10 : 14, static_cast<const uint8_t *>(src), st->ks->d_slots,
                                     st->eng->d_t0, st->d_stage + 48, reinterpret_cast<uint32_t *>(st->d_stage + ECB_DONE),
@@ -198,8 +221,35 @@ static void ctr_transform(ptls_cipher_context_t *_ctx, void *output, const void 
         static_cast<uint8_t *>(output)[i] = static_cast<const uint8_t *>(input)[i] ^ st->bits[i];
 }
 
-/* a one-key ECB state on the plugin engine's device: expanded key slot + 64 B of device / pinned staging */
-static hip_ctr_state *ecb_state_new(const void *key, size_t key_size)
+/* ChaCha20's staging (the 256-B pinned piece): descriptor @0, the 16-byte iv ("sample") @32, the keystream block @48 */
+static const size_t CC_SAMPLE = 32, CC_MASK = 48;
+
+/* ptls_hip_chacha20's do_init: the first 16 keystream bytes of ChaCha20(key, counter = LE32(iv[0..4]), nonce = iv[4..16]) on
+ * the device, one launch of its own (never through the worker) */
+static void chacha_init(ptls_cipher_context_t *_ctx, const void *iv)
+{
+    hip_ctr_state *st = reinterpret_cast<hip_ctr_context *>(_ctx)->st;
+    DeviceGuard g(st->eng->device);
+    const ptls_hip_supp_t sp{CC_SAMPLE, CC_MASK, 0, PTLS_HIP_SUPP_ENABLE};
+    std::memcpy(st->h_stage, &sp, sizeof(sp));
+    std::memcpy(st->h_stage + CC_SAMPLE, iv, 16);
+    hipStream_t stream = pool_stream();
+    const int e = launch_chacha_mask(reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage), 1, st->d_stage, st->d_stage,
+                                     st->ks->d_chacha, 1, 1, stream);
+    if (e != 0) {
+        g_err = hipGetErrorString((hipError_t)e);
+        plugin_die("chacha20 launch");
+    }
+    plugin_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    pool_stream_put(stream);
+    std::memcpy(st->bits, st->h_stage + CC_MASK, 16);
+    std::memset(st->h_stage + CC_SAMPLE, 0, 32);
+    st->ready = true;
+}
+
+/* a one-key cipher state on the plugin engine's device: the key in a one-slot keyset + a 256-B pinned staging piece (the
+ * AES-CTR contexts, fusion's one-block ECB API and ptls_hip_chacha20) */
+static hip_ctr_state *ctr_state_new(keyset_maker make_keyset, const void *key, size_t key_size)
 {
     ptls_hip_engine_t *eng = plugin_engine();
     if (eng == nullptr || key == nullptr)
@@ -207,7 +257,7 @@ static hip_ctr_state *ecb_state_new(const void *key, size_t key_size)
     DeviceGuard g(eng->device);
     auto *st = new hip_ctr_state();
     st->eng = eng;
-    st->ks = pool_keyset(eng, key_size, key, nullptr);
+    st->ks = make_keyset(eng, key_size, key, nullptr);
     if (st->ks == nullptr) {
         delete st;
         return nullptr;
@@ -217,10 +267,10 @@ static hip_ctr_state *ecb_state_new(const void *key, size_t key_size)
     return st;
 }
 
-static void ecb_state_free(hip_ctr_state *st)
+static void ctr_state_free(hip_ctr_state *st)
 {
-    /* the last block's kernel wrote its completion word after its last access to the staging or the slot (plugin_wait):
-     * nothing waits here */
+    /* the last block's kernel wrote its completion word after its last access to the staging or the slot (plugin_wait), or
+     * its stream was synchronized (ChaCha20): nothing waits here */
     ptls_hip_keyset_free(st->ks);
     pool_piece_put(st->h_stage);
     std::memset(st->bits, 0, sizeof(st->bits));
@@ -232,19 +282,20 @@ static void ctr_dispose(ptls_cipher_context_t *_ctx)
     auto *ctx = reinterpret_cast<hip_ctr_context *>(_ctx);
     if (ctx->st == nullptr)
         return;
-    ecb_state_free(ctx->st);
+    ctr_state_free(ctx->st);
     ctx->st = nullptr;
 }
 
-static int aesctr_setup(ptls_cipher_context_t *_ctx, int is_enc, const void *key, size_t key_size)
+/* the setup_crypto of the three cipher objects; do_transform serves at most 16 bytes per do_init for all of them */
+static int cipher_setup(ptls_cipher_context_t *_ctx, keyset_maker make_keyset, const void *key, size_t key_size,
+                        void (*do_init)(ptls_cipher_context_t *, const void *))
 {
-    (void)is_enc; /* CTR: same operation both ways */
     auto *ctx = reinterpret_cast<hip_ctr_context *>(_ctx);
-    ctx->st = ecb_state_new(key, key_size);
+    ctx->st = ctr_state_new(make_keyset, key, key_size);
     if (ctx->st == nullptr)
         return -1;
     ctx->super.do_dispose = ctr_dispose;
-    ctx->super.do_init = ctr_init;
+    ctx->super.do_init = do_init;
     ctx->super.do_transform = ctr_transform;
     return 0;
 }
@@ -261,7 +312,7 @@ extern "C" int ptls_hip_aesecb_init(ptls_hip_aesecb_context_t *ctx, int is_enc, 
     /* fusion asserts encryption-only and a 16- or 32-byte key (lib/fusion.c:859-873) */
     if (!is_enc || key == nullptr || (key_size != PTLS_AES128_KEY_SIZE && key_size != PTLS_AES256_KEY_SIZE))
         return fail(PTLS_HIP_EINVAL, "aesecb_init: encryption with a 16- or 32-byte key only");
-    hip_ctr_state *st = ecb_state_new(key, key_size);
+    hip_ctr_state *st = ctr_state_new(pool_keyset, key, key_size);
     if (st == nullptr)
         return fail(PTLS_HIP_ENODEV, "aesecb_init: %s", g_err.empty() ? "no usable gfx950 device" : g_err.c_str());
     ctx->state = st;
@@ -273,7 +324,7 @@ extern "C" void ptls_hip_aesecb_dispose(ptls_hip_aesecb_context_t *ctx)
 {
     if (ctx == nullptr || ctx->state == nullptr)
         return;
-    ecb_state_free(static_cast<hip_ctr_state *>(ctx->state));
+    ctr_state_free(static_cast<hip_ctr_state *>(ctx->state));
     ctx->state = nullptr;
     ctx->rounds = 0;
 }
@@ -290,16 +341,23 @@ extern "C" void ptls_hip_aesecb_encrypt(ptls_hip_aesecb_context_t *ctx, void *ds
     std::memset(block, 0, sizeof(block));
 }
 
+/* (is_enc: the same operation both ways) */
 static int aes128ctr_setup(ptls_cipher_context_t *ctx, int is_enc, const void *key)
 {
-    return aesctr_setup(ctx, is_enc, key, PTLS_AES128_KEY_SIZE);
+    return cipher_setup(ctx, pool_keyset, key, PTLS_AES128_KEY_SIZE, ctr_init);
 }
 
 static int aes256ctr_setup(ptls_cipher_context_t *ctx, int is_enc, const void *key)
 {
-    return aesctr_setup(ctx, is_enc, key, PTLS_AES256_KEY_SIZE);
+    return cipher_setup(ctx, pool_keyset, key, PTLS_AES256_KEY_SIZE, ctr_init);
 }
 
+static int chacha20_setup(ptls_cipher_context_t *ctx, int is_enc, const void *key)
+{
+    return cipher_setup(ctx, chacha_keyset, key, PTLS_CHACHA20_KEY_SIZE, chacha_init);
+}
+
+/* ---- the AEAD objects: one record per call ------------------------------------------------------ */
 
 static void state_reserve(hip_aead_state *st, size_t len, size_t aadlen)
 {
@@ -336,10 +394,11 @@ extern "C" int ptls_hip_diag_plugin_stamps(uint64_t *out)
 }
 #endif
 
-/* fused header protection for one plugin call: sample offset inside the record output, hp key slots */
+/* fused header protection for one plugin call: sample offset inside the record output, the hp key's keyset (of the AEAD
+ * keyset's algorithm) */
 struct PluginSupp {
     uint64_t sample_off;
-    const KeySlot *hp_slots;
+    const ptls_hip_keyset_t *hp_ks;
     uint8_t *output; /* host: supp->output */
 };
 
@@ -363,11 +422,78 @@ static void stage_record(uint8_t *dst_in, uint8_t *dst_aad, const void *input, s
         std::memcpy(dst_aad, aad, aadlen);
 }
 
-/* run one record: in/out/aad are the caller's (unpinned) host buffers.  The sparse kernel's single-record path (one wave
- * per record, its own 8 KiB H^64 table, none for records of <= 64 GHASH elements; two waves for longer ones) serves it
- * without building a workgroup-wide 64 KiB table; through the worker, no launch at all. */
-static uint64_t plugin_run(hip_aead_state *st, bool open, void *output, const void *input, size_t len, uint64_t seq,
-                           const void *aad, size_t aadlen, const PluginSupp *ps = nullptr, const void *tag = nullptr)
+/* The cipher-specific middle of a launched call: the record `rec` by value in the kernel arguments, its bytes staged in
+ * st->h_io ([in][out][aad], state_reserve), result / supp descriptor / mask in st->h_stage (ST_*); launches on `stream` and
+ * returns when the kernel has finished. */
+
+/* AES-GCM: the sparse kernel's single-record path (one wave per record, its own 8 KiB H^64 table, none for records of <= 64
+ * GHASH elements; two waves for longer ones), no workgroup-wide 64 KiB table; waits on the completion word (plugin_wait) */
+static void launch_aes(hip_aead_state *st, bool open, const ptls_hip_record_t &rec, const PluginSupp *ps, hipStream_t stream)
+{
+    KernelArgs a{};
+    a.one = rec; /* by value in the kernel arguments (recs_ord stays null): the kernel's first dependent host read is
+                    the record's own bytes */
+    a.in = st->d_io;
+    a.aad = st->d_io + st->cap + st->cap + 16;
+    a.out = st->d_io + st->cap;
+    a.result = reinterpret_cast<uint64_t *>(st->d_stage + ST_RESULT);
+    a.slots = st->ks->d_slots;
+    a.basis = st->ks->d_basis;
+    a.t0 = st->eng->d_t0;
+    if (ps != nullptr) {
+        a.supp = reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage + ST_SUPP);
+        a.hp_slots = ps->hp_ks->d_slots;
+        a.hp_nslots = 1;
+        a.mask = st->d_stage + ST_MASK;
+    }
+    a.done = reinterpret_cast<uint32_t *>(st->d_stage + ST_DONE);
+    a.done_seq = ++st->done_seq;
+#if STAMP_PHASES
+    if (g_diag_stamps == nullptr)
+        plugin_check(hipMalloc(&g_diag_stamps, 16 * sizeof(uint64_t)), "hipMalloc(stamps)");
+    a.clk = g_diag_stamps;
+#endif
+    const int e = launch_batch(SPARSE_LANES, st->ks->key_size == 16 ? 10 : 14, open, 0, 1, stream, a, true);
+    if (e != 0) {
+        g_err = hipGetErrorString((hipError_t)e);
+        plugin_die("launch");
+    }
+    plugin_wait(stream, st->h_stage + ST_DONE, a.done_seq);
+}
+
+/* ChaCha20-Poly1305: chacha_kernel.hip on the one record; its kernel has no completion word, so the stream is synchronized */
+static void launch_chacha(hip_aead_state *st, bool open, const ptls_hip_record_t &rec, const PluginSupp *ps, hipStream_t stream)
+{
+    ChaChaArgs a{};
+    a.n = 1;
+    a.one = rec;
+    a.in = st->d_io;
+    a.aad = st->d_io + st->cap + st->cap + 16;
+    a.out = st->d_io + st->cap;
+    a.result = reinterpret_cast<uint64_t *>(st->d_stage + ST_RESULT);
+    a.slots = st->ks->d_chacha;
+    if (ps != nullptr) {
+        a.supp = reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage + ST_SUPP);
+        a.hp_slots = ps->hp_ks->d_chacha;
+        a.hp_nslots = 1;
+        a.mask = st->d_stage + ST_MASK;
+    }
+    /* one record: as many lanes as it has whole ChaCha blocks to give them */
+    const size_t blocks = rec.len / 64;
+    const int lanes = blocks >= 16 ? 64 : blocks >= 4 ? 16 : blocks >= 1 ? 4 : 1;
+    const int e = launch_chacha_batch(lanes, open, stream, a, true);
+    if (e != 0) {
+        g_err = hipGetErrorString((hipError_t)e);
+        plugin_die("chacha20poly1305 launch");
+    }
+    plugin_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+}
+
+/* run one record: in/out/aad are the caller's (unpinned) host buffers.  AES-GCM goes through the resident worker (no launch
+ * at all) unless PTLS_HIP_PLUGIN_WORKER=0; then, and for every ChaCha20-Poly1305 record, the call is one launch of its own.
+ * `tag`: the detached tag of ptls_hip_aesgcm_decrypt (AES only). */
+static uint64_t aead_run(hip_aead_state *st, bool open, void *output, const void *input, size_t len, uint64_t seq,
+                         const void *aad, size_t aadlen, const PluginSupp *ps = nullptr, const void *tag = nullptr)
 {
     DeviceGuard g(st->eng->device);
     const size_t in_len = open ? len + 16 : len, out_len = open ? len : len + 16;
@@ -378,7 +504,7 @@ static uint64_t plugin_run(hip_aead_state *st, bool open, void *output, const vo
     rec.aad_len = (uint32_t)aadlen;
     const ptls_hip_supp_t sp{ps != nullptr ? ps->sample_off : 0, 0, 0, PTLS_HIP_SUPP_ENABLE};
     uint64_t result = len;
-    if (worker_enabled() && !STAMP_PHASES) {
+    if (st->ks->algo == PTLS_HIP_ALGO_AESGCM && worker_enabled() && !STAMP_PHASES) {
         PluginWorker &w = g_worker;
         if (!w.ready.load(std::memory_order_acquire)) {
             std::lock_guard<std::mutex> lk(w.launch_mu);
@@ -412,7 +538,7 @@ static uint64_t plugin_run(hip_aead_state *st, bool open, void *output, const vo
         if (ps != nullptr) {
             std::memcpy(h->aux + WAUX_SUPP, &sp, sizeof(sp));
             rq.supp = reinterpret_cast<const ptls_hip_supp_t *>(d->aux + WAUX_SUPP);
-            rq.hp_slots = ps->hp_slots;
+            rq.hp_slots = ps->hp_ks->d_slots;
             rq.mask = d->aux + WAUX_MASK;
         }
         rq.done = reinterpret_cast<uint32_t *>(d->aux + WAUX_DONE);
@@ -440,7 +566,7 @@ static uint64_t plugin_run(hip_aead_state *st, bool open, void *output, const vo
         w.mbox[j].mu.unlock();
         return result;
     }
-    /* one launch per call (PTLS_HIP_PLUGIN_WORKER=0) */
+    /* one launch per call: the record's bytes in the context's pinned staging, wiped afterwards */
     state_reserve(st, in_len, aadlen);
     if (st->h_stage == nullptr) {
         st->h_stage = pool_piece();
@@ -453,45 +579,22 @@ static uint64_t plugin_run(hip_aead_state *st, bool open, void *output, const vo
         st->iv_dirty = false;
     }
     uint8_t *h_in = st->h_io, *h_out = st->h_io + st->cap, *h_aad = st->h_io + st->cap + st->cap + 16;
-    uint8_t *d_in = st->d_io, *d_out = st->d_io + st->cap, *d_aad = st->d_io + st->cap + st->cap + 16;
-    std::memcpy(st->h_stage + ST_SUPP, &sp, sizeof(sp));
+    if (ps != nullptr)
+        std::memcpy(st->h_stage + ST_SUPP, &sp, sizeof(sp));
     stage_record(h_in, h_aad, input, len, in_len, tag, aad, aadlen);
-    KernelArgs a{};
-    a.one = rec; /* by value in the kernel arguments (recs_ord stays null): the kernel's first dependent host read is
-                    the record's own bytes */
-    a.in = d_in;
-    a.aad = d_aad;
-    a.out = d_out;
-    a.result = reinterpret_cast<uint64_t *>(st->d_stage + ST_RESULT);
-    a.slots = st->ks->d_slots;
-    a.basis = st->ks->d_basis;
-    a.t0 = st->eng->d_t0;
-    if (ps != nullptr) {
-        a.supp = reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage + ST_SUPP);
-        a.hp_slots = ps->hp_slots;
-        a.hp_nslots = 1;
-        a.mask = st->d_stage + ST_MASK;
-    }
-    a.done = reinterpret_cast<uint32_t *>(st->d_stage + ST_DONE);
-    a.done_seq = ++st->done_seq;
-#if STAMP_PHASES
-    if (g_diag_stamps == nullptr)
-        plugin_check(hipMalloc(&g_diag_stamps, 16 * sizeof(uint64_t)), "hipMalloc(stamps)");
-    a.clk = g_diag_stamps;
-#endif
-    const int e = launch_batch(SPARSE_LANES, st->ks->key_size == 16 ? 10 : 14, open, 0, 1, stream, a, true);
-    if (e != 0) {
-        g_err = hipGetErrorString((hipError_t)e);
-        plugin_die("launch");
-    }
-    plugin_wait(stream, st->h_stage + ST_DONE, a.done_seq);
+    if (st->ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305)
+        launch_chacha(st, open, rec, ps, stream);
+    else
+        launch_aes(st, open, rec, ps, stream);
     pool_stream_put(stream);
     if (open)
         std::memcpy(&result, st->h_stage + ST_RESULT, 8);
     if (out_len != 0)
         std::memcpy(output, h_out, out_len);
-    if (ps != nullptr)
+    if (ps != nullptr) {
         std::memcpy(ps->output, st->h_stage + ST_MASK, 16);
+        std::memset(st->h_stage + ST_MASK, 0, 16);
+    }
     /* the record's bytes do not stay in the staging */
     std::memset(h_in, 0, in_len);
     std::memset(h_out, 0, out_len);
@@ -564,18 +667,22 @@ static void encrypt_supp(hip_aead_state *st, void *output, const void *input, si
                          size_t aadlen, ptls_aead_supplementary_encryption_t *supp)
 {
     if (supp != nullptr) {
-        /* fused (lib/fusion.c:424-428, :636-650): our CTR context, same key size, sample inside the output */
+        /* fused (lib/fusion.c:424-428, :636-650): one of our cipher contexts, of the AEAD's algorithm and key size (ChaCha
+         * keys are always 32 bytes), on the same engine, the sample inside the output: the mask comes out of the record's
+         * call */
         const hip_ctr_state *cs = ctr_state_of(supp->ctx);
         const uint8_t *in = static_cast<const uint8_t *>(supp->input), *o = static_cast<const uint8_t *>(output);
-        if (cs != nullptr && cs->ks->key_size == st->ks->key_size && cs->eng == st->eng && in >= o && in + 16 <= o + inlen + 16) {
-            PluginSupp ps{(uint64_t)(in - o), cs->ks->d_slots, supp->output};
-            plugin_run(st, false, output, input, inlen, seq, aad, aadlen, &ps);
+        if (cs != nullptr && cs->ks->algo == st->ks->algo && cs->ks->key_size == st->ks->key_size && cs->eng == st->eng &&
+            in >= o && in + 16 <= o + inlen + 16) {
+            PluginSupp ps{(uint64_t)(in - o), cs->ks, supp->output};
+            aead_run(st, false, output, input, inlen, seq, aad, aadlen, &ps);
             return;
         }
     }
-    plugin_run(st, false, output, input, inlen, seq, aad, aadlen);
+    aead_run(st, false, output, input, inlen, seq, aad, aadlen);
     if (supp != nullptr) {
-        /* header-protection mask from the caller's cipher context, computed after the AEAD output exists
+        /* any other cipher context (another library's, the other cipher, AES with the other key size): the
+         * header-protection mask from the context itself, computed after the AEAD output exists
          * (ptls_aead__do_encrypt, include/picotls.h:2027-2038; fusion fuses it, lib/fusion.c:636-650) */
         supp->ctx->do_init(supp->ctx, supp->input);
         std::memset(supp->output, 0, sizeof(supp->output));
@@ -589,8 +696,8 @@ static void aead_encrypt(ptls_aead_context_t *_ctx, void *output, const void *in
     encrypt_supp(reinterpret_cast<hip_aead_context *>(_ctx)->st, output, input, inlen, seq, aad, aadlen, supp);
 }
 
-static void aead_encrypt_v(ptls_aead_context_t *_ctx, void *output, ptls_iovec_t *input, size_t incnt, uint64_t seq,
-                           const void *aad, size_t aadlen)
+/* the scattered input of do_encrypt_v in one piece */
+static std::vector<uint8_t> flatten(const ptls_iovec_t *input, size_t incnt)
 {
     size_t total = 0;
     for (size_t i = 0; i < incnt; ++i)
@@ -602,7 +709,15 @@ static void aead_encrypt_v(ptls_aead_context_t *_ctx, void *output, ptls_iovec_t
             std::memcpy(flat.data() + off, input[i].base, input[i].len);
         off += input[i].len;
     }
-    plugin_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, false, output, flat.data(), total, seq, aad, aadlen);
+    return flat;
+}
+
+static void aead_encrypt_v(ptls_aead_context_t *_ctx, void *output, ptls_iovec_t *input, size_t incnt, uint64_t seq,
+                           const void *aad, size_t aadlen)
+{
+    std::vector<uint8_t> flat = flatten(input, incnt);
+    aead_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, false, output, flat.data(), flat.size(), seq, aad, aadlen);
+    std::fill(flat.begin(), flat.end(), 0); /* the plaintext copy does not stay in freed memory */
 }
 
 static size_t aead_decrypt(ptls_aead_context_t *_ctx, void *output, const void *input, size_t inlen, uint64_t seq, const void *aad,
@@ -610,13 +725,13 @@ static size_t aead_decrypt(ptls_aead_context_t *_ctx, void *output, const void *
 {
     if (inlen < 16)
         return SIZE_MAX;
-    const uint64_t r = plugin_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, true, output, input, inlen - 16, seq, aad, aadlen);
+    const uint64_t r = aead_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, true, output, input, inlen - 16, seq, aad, aadlen);
     return r == ~(uint64_t)0 ? SIZE_MAX : (size_t)r;
 }
 
-/* one single-record AEAD state on the plugin engine's device (shared by the plugin contexts and the
- * fusion-style low-level API) */
-static hip_aead_state *state_new(const void *key, const void *iv, size_t key_size)
+/* one single-record AEAD state on the plugin engine's device, its keyset from make_keyset (shared by the plugin contexts
+ * and the fusion-style low-level API) */
+static hip_aead_state *state_new(keyset_maker make_keyset, const void *key, const void *iv, size_t key_size)
 {
     ptls_hip_engine_t *eng = plugin_engine();
     if (eng == nullptr)
@@ -624,7 +739,7 @@ static hip_aead_state *state_new(const void *key, const void *iv, size_t key_siz
     DeviceGuard g(eng->device);
     auto *st = new hip_aead_state();
     st->eng = eng;
-    st->ks = pool_keyset(eng, key_size, key, iv);
+    st->ks = make_keyset(eng, key_size, key, iv);
     if (st->ks == nullptr) {
         delete st;
         return nullptr;
@@ -634,9 +749,10 @@ static hip_aead_state *state_new(const void *key, const void *iv, size_t key_siz
     return st;
 }
 
-static int aesgcm_setup(ptls_aead_context_t *_ctx, int is_enc, const void *key, const void *iv, size_t key_size)
+/* the setup_crypto of every AEAD object: one context seals and opens, whatever is_enc says, as fusion's
+ * (lib/fusion.c:1184-1206) */
+static int aead_setup(ptls_aead_context_t *_ctx, keyset_maker make_keyset, const void *key, const void *iv, size_t key_size)
 {
-    (void)is_enc; /* one context seals and opens, as fusion's (lib/fusion.c:1184-1206) */
     auto *ctx = reinterpret_cast<hip_aead_context *>(_ctx);
     if (key == nullptr) {
         /* IV-only setup: fusion stores the IV and returns 0, on a fresh context as on a keyed one
@@ -657,7 +773,7 @@ static int aesgcm_setup(ptls_aead_context_t *_ctx, int is_enc, const void *key, 
     }
     if (_ctx->dispose_crypto != nullptr && ctx->st != nullptr) /* re-keying a keyed context: release the old key first */
         aead_dispose(_ctx);
-    ctx->st = state_new(key, iv, key_size);
+    ctx->st = state_new(make_keyset, key, iv, key_size);
     if (ctx->st == nullptr)
         return -1;
     ctx->super.dispose_crypto = aead_dispose;
@@ -674,12 +790,17 @@ static int aesgcm_setup(ptls_aead_context_t *_ctx, int is_enc, const void *key, 
 
 static int aes128gcm_setup(ptls_aead_context_t *ctx, int is_enc, const void *key, const void *iv)
 {
-    return aesgcm_setup(ctx, is_enc, key, iv, PTLS_AES128_KEY_SIZE);
+    return aead_setup(ctx, pool_keyset, key, iv, PTLS_AES128_KEY_SIZE);
 }
 
 static int aes256gcm_setup(ptls_aead_context_t *ctx, int is_enc, const void *key, const void *iv)
 {
-    return aesgcm_setup(ctx, is_enc, key, iv, PTLS_AES256_KEY_SIZE);
+    return aead_setup(ctx, pool_keyset, key, iv, PTLS_AES256_KEY_SIZE);
+}
+
+static int chacha20poly1305_setup(ptls_aead_context_t *ctx, int is_enc, const void *key, const void *iv)
+{
+    return aead_setup(ctx, chacha_keyset, key, iv, PTLS_CHACHA20_KEY_SIZE);
 }
 
 /* ptls_non_temporal_aes{128,256}gcm's contract (non_temporal_setup, lib/fusion.c:2109-2142): an encrypt
@@ -688,7 +809,7 @@ static int aes256gcm_setup(ptls_aead_context_t *ctx, int is_enc, const void *key
  * only in its x86 store and reduction strategy), so the records run through the same kernel. */
 static int non_temporal_setup(ptls_aead_context_t *_ctx, int is_enc, const void *key, const void *iv, size_t key_size)
 {
-    const int ret = aesgcm_setup(_ctx, is_enc, key, iv, key_size);
+    const int ret = aead_setup(_ctx, pool_keyset, key, iv, key_size);
     if (ret != 0 || key == nullptr)
         return ret;
     _ctx->do_encrypt_init = nullptr;
@@ -711,242 +832,6 @@ static int non_temporal_aes128gcm_setup(ptls_aead_context_t *ctx, int is_enc, co
 static int non_temporal_aes256gcm_setup(ptls_aead_context_t *ctx, int is_enc, const void *key, const void *iv)
 {
     return non_temporal_setup(ctx, is_enc, key, iv, PTLS_AES256_KEY_SIZE);
-}
-
-/* ---------------------------------------------------------------------------------------------- */
-/* ptls_hip_chacha20poly1305 / ptls_hip_chacha20 (replace ptls_minicrypto_chacha20poly1305 / _chacha20,  */
-/* lib/cifra/chacha20.c:44-113): one launch of chacha_kernel.hip per call, never through the worker      */
-/* ---------------------------------------------------------------------------------------------- */
-
-extern "C" ptls_cipher_algorithm_t ptls_hip_chacha20;
-
-/* a one-slot ChaCha keyset of its own (44 bytes of device memory; the plugin's slot pool holds AES slots) */
-static ptls_hip_keyset_t *chacha_keyset(ptls_hip_engine_t *eng, const void *key, const void *iv)
-{
-    ptls_hip_keyset_t *ks = ptls_hip_keyset_new_algo(eng, PTLS_HIP_ALGO_CHACHA20POLY1305, PTLS_CHACHA20_KEY_SIZE, 1);
-    if (ks == nullptr)
-        return nullptr;
-    hipStream_t stream = pool_stream();
-    const int rc = ptls_hip_keyset_set(ks, 0, 1, key, iv, stream);
-    pool_stream_put(stream);
-    if (rc != 0) {
-        ptls_hip_keyset_free(ks);
-        return nullptr;
-    }
-    return ks;
-}
-
-/* the cipher's staging (a 256-B pinned piece): descriptor @0, the 16-byte iv ("sample") @32, the keystream block @48 */
-static const size_t CC_SAMPLE = 32, CC_MASK = 48;
-
-/* do_init: the first 16 keystream bytes of ChaCha20(key, counter = LE32(iv[0..4]), nonce = iv[4..16]) on the device */
-static void chacha_init(ptls_cipher_context_t *_ctx, const void *iv)
-{
-    hip_ctr_state *st = reinterpret_cast<hip_ctr_context *>(_ctx)->st;
-    DeviceGuard g(st->eng->device);
-    const ptls_hip_supp_t sp{CC_SAMPLE, CC_MASK, 0, PTLS_HIP_SUPP_ENABLE};
-    std::memcpy(st->h_stage, &sp, sizeof(sp));
-    std::memcpy(st->h_stage + CC_SAMPLE, iv, 16);
-    hipStream_t stream = pool_stream();
-    const int e = launch_chacha_mask(reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage), 1, st->d_stage, st->d_stage,
-                                     st->ks->d_chacha, 1, 1, stream);
-    if (e != 0) {
-        g_err = hipGetErrorString((hipError_t)e);
-        plugin_die("chacha20 launch");
-    }
-    plugin_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    pool_stream_put(stream);
-    std::memcpy(st->bits, st->h_stage + CC_MASK, 16);
-    std::memset(st->h_stage + CC_SAMPLE, 0, 32);
-    st->ready = true;
-}
-
-static void chacha_cipher_dispose(ptls_cipher_context_t *_ctx)
-{
-    auto *ctx = reinterpret_cast<hip_ctr_context *>(_ctx);
-    if (ctx->st == nullptr)
-        return;
-    ecb_state_free(ctx->st); /* keyset (zeroized), staging piece, keystream bits */
-    ctx->st = nullptr;
-}
-
-static int chacha20_setup(ptls_cipher_context_t *_ctx, int is_enc, const void *key)
-{
-    (void)is_enc;
-    auto *ctx = reinterpret_cast<hip_ctr_context *>(_ctx);
-    ctx->st = nullptr;
-    ptls_hip_engine_t *eng = plugin_engine();
-    if (eng == nullptr || key == nullptr)
-        return -1;
-    DeviceGuard g(eng->device);
-    auto *st = new hip_ctr_state();
-    st->eng = eng;
-    st->ks = chacha_keyset(eng, key, nullptr);
-    if (st->ks == nullptr) {
-        delete st;
-        return -1;
-    }
-    st->h_stage = pool_piece();
-    st->d_stage = mapped_or_die(st->h_stage);
-    ctx->st = st;
-    ctx->super.do_dispose = chacha_cipher_dispose;
-    ctx->super.do_init = chacha_init;
-    ctx->super.do_transform = ctr_transform; /* at most 16 bytes per do_init, as the AES objects */
-    return 0;
-}
-
-/* one record through its own launch: the record by value, its bytes in the context's pinned staging, wiped afterwards */
-static uint64_t chacha_run(hip_aead_state *st, bool open, void *output, const void *input, size_t len, uint64_t seq,
-                           const void *aad, size_t aadlen, const hip_ctr_state *hp = nullptr, uint64_t sample_off = 0,
-                           uint8_t *mask_out = nullptr)
-{
-    DeviceGuard g(st->eng->device);
-    const size_t in_len = open ? len + 16 : len, out_len = open ? len : len + 16;
-    state_reserve(st, in_len, aadlen);
-    if (st->h_stage == nullptr) {
-        st->h_stage = pool_piece();
-        st->d_stage = mapped_or_die(st->h_stage);
-    }
-    hipStream_t stream = pool_stream();
-    if (st->iv_dirty) {
-        if (ptls_hip_keyset_set_iv(st->ks, 0, st->iv, stream) != 0)
-            plugin_die("set_iv");
-        st->iv_dirty = false;
-    }
-    uint8_t *h_in = st->h_io, *h_out = st->h_io + st->cap, *h_aad = st->h_io + st->cap + st->cap + 16;
-    stage_record(h_in, h_aad, input, len, in_len, nullptr, aad, aadlen);
-    ChaChaArgs a{};
-    a.n = 1;
-    a.one.seq = seq;
-    a.one.len = (uint32_t)len;
-    a.one.aad_len = (uint32_t)aadlen;
-    a.in = st->d_io;
-    a.out = st->d_io + st->cap;
-    a.aad = st->d_io + st->cap + st->cap + 16;
-    a.result = reinterpret_cast<uint64_t *>(st->d_stage + ST_RESULT);
-    a.slots = st->ks->d_chacha;
-    if (hp != nullptr) {
-        const ptls_hip_supp_t sp{sample_off, 0, 0, PTLS_HIP_SUPP_ENABLE};
-        std::memcpy(st->h_stage + ST_SUPP, &sp, sizeof(sp));
-        a.supp = reinterpret_cast<const ptls_hip_supp_t *>(st->d_stage + ST_SUPP);
-        a.hp_slots = hp->ks->d_chacha;
-        a.hp_nslots = 1;
-        a.mask = st->d_stage + ST_MASK;
-    }
-    /* one record: as many lanes as it has whole ChaCha blocks to give them */
-    const size_t blocks = len / 64;
-    const int lanes = blocks >= 16 ? 64 : blocks >= 4 ? 16 : blocks >= 1 ? 4 : 1;
-    const int e = launch_chacha_batch(lanes, open, stream, a, true);
-    if (e != 0) {
-        g_err = hipGetErrorString((hipError_t)e);
-        plugin_die("chacha20poly1305 launch");
-    }
-    plugin_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    pool_stream_put(stream);
-    uint64_t result = len;
-    if (open)
-        std::memcpy(&result, st->h_stage + ST_RESULT, 8);
-    if (out_len != 0)
-        std::memcpy(output, h_out, out_len);
-    if (hp != nullptr) {
-        std::memcpy(mask_out, st->h_stage + ST_MASK, 16);
-        std::memset(st->h_stage + ST_MASK, 0, 16);
-    }
-    std::memset(h_in, 0, in_len);
-    std::memset(h_out, 0, out_len);
-    return result;
-}
-
-static void chacha_aead_encrypt(ptls_aead_context_t *_ctx, void *output, const void *input, size_t inlen, uint64_t seq,
-                                const void *aad, size_t aadlen, ptls_aead_supplementary_encryption_t *supp)
-{
-    hip_aead_state *st = reinterpret_cast<hip_aead_context *>(_ctx)->st;
-    if (supp != nullptr && supp->ctx != nullptr && supp->ctx->algo == &ptls_hip_chacha20) {
-        /* our ChaCha20 context and a sample inside the output: the mask comes out of the record's launch */
-        const hip_ctr_state *cs = reinterpret_cast<const hip_ctr_context *>(supp->ctx)->st;
-        const uint8_t *in = static_cast<const uint8_t *>(supp->input), *o = static_cast<const uint8_t *>(output);
-        if (cs != nullptr && cs->eng == st->eng && in >= o && in + 16 <= o + inlen + 16) {
-            chacha_run(st, false, output, input, inlen, seq, aad, aadlen, cs, (uint64_t)(in - o), supp->output);
-            return;
-        }
-    }
-    chacha_run(st, false, output, input, inlen, seq, aad, aadlen);
-    if (supp != nullptr) { /* any other cipher context: ptls_aead__do_encrypt's order (include/picotls.h:2027-2038) */
-        supp->ctx->do_init(supp->ctx, supp->input);
-        std::memset(supp->output, 0, sizeof(supp->output));
-        supp->ctx->do_transform(supp->ctx, supp->output, supp->output, sizeof(supp->output));
-    }
-}
-
-static void chacha_aead_encrypt_v(ptls_aead_context_t *_ctx, void *output, ptls_iovec_t *input, size_t incnt, uint64_t seq,
-                                  const void *aad, size_t aadlen)
-{
-    size_t total = 0;
-    for (size_t i = 0; i < incnt; ++i)
-        total += input[i].len;
-    std::vector<uint8_t> flat(total);
-    size_t off = 0;
-    for (size_t i = 0; i < incnt; ++i) {
-        if (input[i].len != 0)
-            std::memcpy(flat.data() + off, input[i].base, input[i].len);
-        off += input[i].len;
-    }
-    chacha_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, false, output, flat.data(), total, seq, aad, aadlen);
-    std::fill(flat.begin(), flat.end(), 0);
-}
-
-static size_t chacha_aead_decrypt(ptls_aead_context_t *_ctx, void *output, const void *input, size_t inlen, uint64_t seq,
-                                  const void *aad, size_t aadlen)
-{
-    if (inlen < 16)
-        return SIZE_MAX;
-    const uint64_t r = chacha_run(reinterpret_cast<hip_aead_context *>(_ctx)->st, true, output, input, inlen - 16, seq, aad, aadlen);
-    return r == ~(uint64_t)0 ? SIZE_MAX : (size_t)r;
-}
-
-static int chacha20poly1305_setup(ptls_aead_context_t *_ctx, int is_enc, const void *key, const void *iv)
-{
-    (void)is_enc;
-    auto *ctx = reinterpret_cast<hip_aead_context *>(_ctx);
-    if (key == nullptr) { /* IV-only setup, on a fresh context as on a keyed one (as aesgcm_setup above) */
-        if (_ctx->dispose_crypto == nullptr) {
-            ctx->st = nullptr;
-            std::memcpy(ctx->iv, iv, 12);
-            ctx->super.dispose_crypto = aead_dispose;
-            ctx->super.do_get_iv = aead_get_iv;
-            ctx->super.do_set_iv = aead_set_iv;
-            return 0;
-        }
-        aead_set_iv(_ctx, iv);
-        return 0;
-    }
-    if (_ctx->dispose_crypto != nullptr && ctx->st != nullptr)
-        aead_dispose(_ctx);
-    ctx->st = nullptr;
-    ptls_hip_engine_t *eng = plugin_engine();
-    if (eng == nullptr)
-        return -1;
-    DeviceGuard g(eng->device);
-    auto *st = new hip_aead_state();
-    st->eng = eng;
-    st->ks = chacha_keyset(eng, key, iv);
-    if (st->ks == nullptr) {
-        delete st;
-        return -1;
-    }
-    std::memcpy(st->iv, iv, 12);
-    st->iv_dirty = false;
-    ctx->st = st;
-    ctx->super.dispose_crypto = aead_dispose;
-    ctx->super.do_get_iv = aead_get_iv;
-    ctx->super.do_set_iv = aead_set_iv;
-    ctx->super.do_encrypt_init = aead_encrypt_init;
-    ctx->super.do_encrypt_update = aead_encrypt_update;
-    ctx->super.do_encrypt_final = aead_encrypt_final;
-    ctx->super.do_encrypt = chacha_aead_encrypt;
-    ctx->super.do_encrypt_v = chacha_aead_encrypt_v;
-    ctx->super.do_decrypt = chacha_aead_decrypt;
-    return 0;
 }
 
 /* Field for field the values of ptls_minicrypto_chacha20 / ptls_minicrypto_chacha20poly1305 (lib/cifra/chacha20.c:97-113). */
@@ -1060,7 +945,7 @@ extern "C" ptls_hip_aesgcm_context_t *ptls_hip_aesgcm_new(const void *key, size_
     if (key == nullptr || (key_size != PTLS_AES128_KEY_SIZE && key_size != PTLS_AES256_KEY_SIZE))
         return nullptr;
     static const uint8_t zero_iv[12] = {0};
-    hip_aead_state *st = state_new(key, zero_iv, key_size);
+    hip_aead_state *st = state_new(pool_keyset, key, zero_iv, key_size);
     if (st == nullptr)
         return nullptr;
     auto *ctx = new ptls_hip_aesgcm_context{st};
@@ -1096,5 +981,5 @@ extern "C" int ptls_hip_aesgcm_decrypt(ptls_hip_aesgcm_context_t *ctx, void *out
                                        const void *nonce, const void *aad, size_t aadlen, const void *tag)
 {
     const uint64_t seq = lowlevel_seq(ctx->st, nonce);
-    return plugin_run(ctx->st, true, output, input, inlen, seq, aad, aadlen, nullptr, tag) != ~(uint64_t)0;
+    return aead_run(ctx->st, true, output, input, inlen, seq, aad, aadlen, nullptr, tag) != ~(uint64_t)0;
 }

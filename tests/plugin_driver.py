@@ -1,8 +1,8 @@
 """Drive an AEAD engine the way a picotls application does, using the REFERENCE's own lifecycle code.
 
 ptls_aead_new_direct / ptls_aead_free / ptls_aead_xor_iv come from oracle/_ref/libptls_fusion_ref.so
-(lib/picotls.c:6458-6490, compiled unmodified); the algorithm object is ptls_hip_aes{128,256}gcm from
-libptls_hip.so.  The inline dispatchers of include/picotls.h:1993-2055 (ptls_aead_encrypt,
+(lib/picotls.c:6458-6490, compiled unmodified); the algorithm object is ptls_hip_aes{128,256}gcm or
+ptls_hip_chacha20poly1305 from libptls_hip.so.  The inline dispatchers of include/picotls.h:1993-2055 (ptls_aead_encrypt,
 ptls_aead_encrypt_v, ptls_aead_decrypt) are one indirect call each; they are reproduced here with
 ctypes through the ptls_aead_context_t vtable.
 """
@@ -52,14 +52,16 @@ class PluginDriver:
         self.ref.ptls_cipher_new.argtypes = [c.c_void_p, c.c_int, c.c_void_p]
         self.ref.ptls_cipher_free.argtypes = [c.c_void_p]
         self.algos = {128: c.addressof(c.c_char.in_dll(hip, "ptls_hip_aes128gcm")),
-                      256: c.addressof(c.c_char.in_dll(hip, "ptls_hip_aes256gcm"))}
+                      256: c.addressof(c.c_char.in_dll(hip, "ptls_hip_aes256gcm")),
+                      "chacha20poly1305": c.addressof(c.c_char.in_dll(hip, "ptls_hip_chacha20poly1305"))}
         self.nt_algos = {128: c.addressof(c.c_char.in_dll(hip, "ptls_hip_non_temporal_aes128gcm")),
                          256: c.addressof(c.c_char.in_dll(hip, "ptls_hip_non_temporal_aes256gcm"))}
         self.ctr_algos = {128: c.addressof(c.c_char.in_dll(hip, "ptls_hip_aes128ctr")),
-                          256: c.addressof(c.c_char.in_dll(hip, "ptls_hip_aes256ctr"))}
+                          256: c.addressof(c.c_char.in_dll(hip, "ptls_hip_aes256ctr")),
+                          "chacha20": c.addressof(c.c_char.in_dll(hip, "ptls_hip_chacha20"))}
 
     def cipher_new(self, bits, key, is_enc=1):
-        """ptls_cipher_new (lib/picotls.c) on ptls_hip_aes{128,256}ctr"""
+        """ptls_cipher_new (lib/picotls.c) on ptls_hip_aes{128,256}ctr (bits 128 / 256) or ptls_hip_chacha20 ("chacha20")"""
         ctx = self.ref.ptls_cipher_new(self.ctr_algos[bits], is_enc, key)
         assert ctx, "ptls_cipher_new returned NULL: " + ptls_hip.last_error()
         return ctx

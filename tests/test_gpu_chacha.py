@@ -506,21 +506,13 @@ import ctypes as c, hashlib, importlib.util, json, os, sys
 sys.path[:0] = {paths!r}
 import ptls_hip, chacha_ref
 import plugin_driver as pd
-from oracle_lib import REF_SO
+from oracle_lib import Oracle
 root = {root!r}
 spec = importlib.util.spec_from_file_location("g", os.path.join(root, "tests", "golden", "make_chacha_golden.py"))
 gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
 gold = json.load(open(os.path.join(root, "tests", "golden", "chacha20poly1305.json")))
-hip, ref = ptls_hip.lib(), c.CDLL(REF_SO)
-ref.ptls_aead_new_direct.restype = c.c_void_p
-ref.ptls_aead_new_direct.argtypes = [c.c_void_p, c.c_int, c.c_void_p, c.c_void_p]
-ref.ptls_aead_free.argtypes = [c.c_void_p]
-ref.ptls_cipher_new.restype = c.c_void_p
-ref.ptls_cipher_new.argtypes = [c.c_void_p, c.c_int, c.c_void_p]
-ref.ptls_cipher_free.argtypes = [c.c_void_p]
-aead = c.addressof(c.c_char.in_dll(hip, "ptls_hip_chacha20poly1305"))
-cipher = c.addressof(c.c_char.in_dll(hip, "ptls_hip_chacha20"))
-drv = pd.PluginDriver.__new__(pd.PluginDriver)  # the vtable dispatchers only: its __init__ binds the AES objects
+drv = pd.PluginDriver()
+AEAD, CIPHER = "chacha20poly1305", "chacha20"
 calls = 0
 # the fixture's records of the plugin lengths, through ptls_aead_new_direct / ptls_aead_encrypt / ptls_aead_decrypt
 want_lens = {{0, 1, 63, 64, 65, 1500, 16384}}
@@ -528,8 +520,7 @@ for e in gold["records"]:
     if e["L"] not in want_lens:
         continue
     key, iv, seq, aad, pt = gen.record_inputs(e["i"])
-    enc, dec = ref.ptls_aead_new_direct(aead, 1, key, iv), ref.ptls_aead_new_direct(aead, 0, key, iv)
-    assert enc and dec, ptls_hip.last_error()
+    enc, dec = drv.new(AEAD, key, iv, 1), drv.new(AEAD, key, iv, 0)  # (asserts that the context exists)
     out = drv.encrypt(enc, pt, seq, aad)
     assert hashlib.sha256(out).hexdigest() == e["sha256"] and out.hex() == e.get("out", out.hex()), ("encrypt", e["i"])
     assert drv.decrypt(dec, out, seq, aad) == pt, ("decrypt", e["i"])
@@ -537,12 +528,12 @@ for e in gold["records"]:
     assert drv.decrypt(dec, bytes(bad), seq, aad) is None, ("bad tag", e["i"])
     parts = [pt[: len(pt) // 3], pt[len(pt) // 3:]]
     assert drv.encrypt_v(enc, parts, seq, aad) == out, ("encrypt_v", e["i"])
-    ref.ptls_aead_free(enc); ref.ptls_aead_free(dec)
+    drv.free(enc); drv.free(dec)
     calls += 1
 assert calls >= 7 * 2, calls
 key, iv, seq, aad, pt = gen.record_inputs(7)
 pt, seq, aad = (pt * 1500)[:1500] or bytes(1500), (1 << 64) - 1, b"\x17\x03\x03\x05\xec"
-enc = ref.ptls_aead_new_direct(aead, 1, key, iv)
+enc = drv.new(AEAD, key, iv)
 assert drv.encrypt(enc, pt, seq, aad) == chacha_ref.seal(key, iv, seq, aad, pt)
 # IV-only re-setup (key NULL) through the algorithm's setup_crypto: the context then seals under the new IV
 class Algo(c.Structure):
@@ -550,21 +541,36 @@ class Algo(c.Structure):
                 ("key_size", c.c_size_t), ("iv_size", c.c_size_t), ("tag_size", c.c_size_t), ("fixed_iv", c.c_size_t),
                 ("record_iv", c.c_size_t), ("nt_and_align_bits", c.c_uint64), ("context_size", c.c_size_t),
                 ("setup", c.c_void_p)]
-setup = c.CFUNCTYPE(c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p)(Algo.from_address(aead).setup)
+setup = c.CFUNCTYPE(c.c_int, c.c_void_p, c.c_int, c.c_void_p, c.c_void_p)(Algo.from_address(drv.algos[AEAD]).setup)
 iv2 = bytes(b ^ 0x5a for b in iv)
 assert setup(enc, 1, None, iv2) == 0
 assert drv.encrypt(enc, pt, 5, aad) == chacha_ref.seal(key, iv2, 5, aad, pt)
-ref.ptls_aead_free(enc)
+drv.free(enc)
 # supp with a ptls_hip_chacha20 context: the fixture's masks (ptls_aead_encrypt_s), and the cipher on its own
 for e in gold["masks"]:
     key, iv, seq, aad, pt, hp_key, sample_off = gen.mask_inputs(e["j"])
-    enc, hp = ref.ptls_aead_new_direct(aead, 1, key, iv), ref.ptls_cipher_new(cipher, 1, hp_key)
-    assert enc and hp, ptls_hip.last_error()
+    enc, hp = drv.new(AEAD, key, iv), drv.cipher_new(CIPHER, hp_key)
     out, mask = drv.encrypt_s(enc, pt, seq, aad, hp, sample_off)
     assert hashlib.sha256(out).hexdigest() == e["sha256"] and mask.hex() == e["mask"], ("supp", e["j"])
     assert drv.cipher_encrypt(hp, out[sample_off: sample_off + 16], bytes(5)) == mask[:5], ("cipher", e["j"])
-    ref.ptls_cipher_free(hp); ref.ptls_aead_free(enc)
+    drv.cipher_free(hp); drv.free(enc)
     calls += 1
+# supp with a cipher context the AEAD's launch cannot serve (the other cipher, or AES with the other key size): the record is
+# the plain encrypt's and the mask comes from the context's own do_init / do_transform (ptls_aead__do_encrypt's order)
+aes_mask = Oracle().aes_ecb
+key, iv, seq, aad, pt, hp_key, _ = gen.mask_inputs(0)
+pt, aad = (hashlib.sha256(b"cross-cipher supp").digest() * 4)[:100], b"\x17\x03\x03\x00\x74"
+for a, akey, ci, ckey, want_mask in ((AEAD, key, 128, hp_key[:16], aes_mask),
+                                     (128, key[:16], CIPHER, hp_key, chacha_ref.hp_mask),
+                                     (128, key[:16], 256, hp_key, aes_mask)):
+    enc, hp = drv.new(a, akey, iv), drv.cipher_new(ci, ckey)
+    plain = drv.encrypt(enc, pt, seq, aad)
+    for sample_off in (0, len(pt)):
+        out, mask = drv.encrypt_s(enc, pt, seq, aad, hp, sample_off)
+        assert out == plain, ("cross supp record", a, ci, sample_off)
+        assert mask == want_mask(ckey, plain[sample_off: sample_off + 16]), ("cross supp mask", a, ci, sample_off)
+        calls += 1
+    drv.cipher_free(hp); drv.free(enc)
 print("ok", calls)
 """
 
