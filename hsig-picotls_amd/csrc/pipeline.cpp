@@ -34,6 +34,11 @@ struct PipeSlot {
      * where they go in d_out, pinned and on the device */
     uint8_t *h_gap, *d_gap;
     GapPiece *h_gapd, *d_gapd;
+    /* copy transport, allocated on a slice with header protection: the slice's masks arrive here, packed, by one copy;
+     * mask t goes to mask_host + mask_dst[t] once the slice is done (slot_wait) */
+    uint8_t *h_mask;
+    uint8_t *mask_host;
+    std::vector<uint64_t> mask_dst;
     bool busy;
 };
 
@@ -110,6 +115,7 @@ extern "C" void ptls_hip_pipeline_free(ptls_hip_pipeline_t *p)
         (void)hipFree(s.d_gap);
         (void)hipHostFree(s.h_gapd);
         (void)hipFree(s.d_gapd);
+        (void)hipHostFree(s.h_mask);
         if (s.done != nullptr)
             (void)hipEventDestroy(s.done);
         if (s.stream != nullptr)
@@ -334,6 +340,7 @@ static void drain_slots(ptls_hip_pipeline_t *p)
         if (s.busy)
             (void)hipStreamSynchronize(s.stream);
         s.busy = false;
+        s.mask_dst.clear(); /* the call failed: masks that were not delivered yet are not delivered */
     }
 }
 
@@ -446,6 +453,45 @@ static bool spans_hit(const std::vector<Span> &uni, uint64_t lo, uint64_t hi)
     return it != uni.end() && it->lo < hi;
 }
 
+/* ---- the copy transport's masks: exactly the records' 16 bytes ------------------------------------------------------- *
+ * h_mask belongs to every slice of the call at once: mask offsets are the caller's choice, so the masks of different
+ * slices may interleave.  A slice therefore neither uploads nor copies back a span of h_mask (bytes of another slice's
+ * masks in that span would come back stale, whenever that slice delivered them in between: slices overlap on pinned
+ * buffers).  The kernel writes the slice's masks packed into d_mask (slice-local mask_off = 16 x the mask's index
+ * among the slice's enabled descriptors with a valid hp_key; the others are skipped by the kernel and have no place
+ * there), ONE copy brings them into the slot's pinned h_mask, and the host places each at the caller's mask_off when it
+ * has waited for the slice (16 bytes per packet, next to the planning the host does per record anyway).  So the number
+ * of copies per slice does not depend on the layout of the masks, no byte of h_mask other than those masks is read or
+ * written, and a slice's masks may lie anywhere in h_mask. */
+static size_t slot_max_masks(const ptls_hip_pipeline_t *p)
+{
+    return p->slice_bytes / 64; /* d_mask holds slice_bytes / 4 */
+}
+
+static int slot_mask_buffer(ptls_hip_pipeline_t *p, PipeSlot &s)
+{
+    if (s.h_mask != nullptr)
+        return 0;
+    if (hipHostMalloc(&s.h_mask, slot_max_masks(p) * 16, hipHostMallocDefault) != hipSuccess) {
+        s.h_mask = nullptr;
+        return fail(PTLS_HIP_ENOMEM, "pipeline: cannot allocate the copy transport's mask staging");
+    }
+    return 0;
+}
+
+/* wait for the slot's slice and deliver its masks */
+static int slot_wait(PipeSlot &s)
+{
+    if (!s.busy)
+        return 0;
+    HIP_TRY(hipEventSynchronize(s.done), PTLS_HIP_ENODEV);
+    for (size_t t = 0; t < s.mask_dst.size(); ++t)
+        std::memcpy(s.mask_host + s.mask_dst[t], s.h_mask + 16 * t, 16);
+    s.mask_dst.clear();
+    s.busy = false;
+    return 0;
+}
+
 static int slot_gap_buffers(ptls_hip_pipeline_t *p, PipeSlot &s)
 {
     if (s.h_gap != nullptr)
@@ -503,9 +549,13 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
     while (i < n) {
         /* grow the slice while every span fits the staging buffers */
         Span in{UINT64_MAX, 0}, out{UINT64_MAX, 0}, ad{UINT64_MAX, 0};
-        size_t j = i;
+        size_t j = i, nmask = 0;
         while (j < n && j - i < p->max_recs - 1) {
             const ptls_hip_record_t &r = recs[j];
+            /* a mask the kernel will write (it skips disabled descriptors and hp keys outside the keyset) */
+            const bool masked = supp != nullptr && (supp[j].flags & PTLS_HIP_SUPP_ENABLE) && supp[j].hp_key < hp_ks->nslots;
+            if (masked && nmask == slot_max_masks(p))
+                break; /* the mask staging is full (nmask != 0, so j > i) */
             Span ni{std::min(in.lo, r.in_off), std::max(in.hi, r.in_off + r.len + tag_in)};
             Span no{std::min(out.lo, r.out_off), std::max(out.hi, r.out_off + r.len + tag_out)};
             Span na{std::min(ad.lo, r.aad_off), std::max(ad.hi, r.aad_off + r.aad_len)};
@@ -521,14 +571,14 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
             in = ni;
             out = no;
             ad = na;
+            nmask += masked;
             ++j;
         }
         if (in.hi - in.lo > p->slice_bytes || out.hi - out.lo > p->slice_bytes || (ad.hi > ad.lo && ad.hi - ad.lo > p->slice_bytes / 4))
             return fail(PTLS_HIP_EINVAL, "pipeline: record %zu does not fit a %zu-byte slice", i, p->slice_bytes);
         if (ad.hi <= ad.lo)
             ad = Span{0, 0};
-        /* header protection: masks land in their own span; every enabled sample must lie in the slice's output */
-        Span mk{UINT64_MAX, 0};
+        /* header protection: every enabled sample must lie in the slice's output */
         if (supp != nullptr) {
             for (size_t t = i; t < j; ++t) {
                 const ptls_hip_supp_t &sp = supp[t];
@@ -536,17 +586,11 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
                     continue;
                 if (sp.sample_off < out.lo || sp.sample_off + 16 > out.hi)
                     return fail(PTLS_HIP_EINVAL, "pipeline_seal_supp: sample of record %zu is outside the slice's output", t);
-                mk = Span{std::min(mk.lo, sp.mask_off), std::max(mk.hi, sp.mask_off + 16)};
             }
-            if (mk.hi > mk.lo && mk.hi - mk.lo > p->slice_bytes / 4)
-                return fail(PTLS_HIP_EINVAL, "pipeline_seal_supp: masks of records %zu..%zu span more than %zu bytes", i, j,
-                            p->slice_bytes / 4);
-            if (mk.hi <= mk.lo)
-                mk = Span{0, 0};
         }
         PipeSlot &s = p->slot[k % NSLOT];
-        if (s.busy)
-            HIP_TRY(hipEventSynchronize(s.done), PTLS_HIP_ENODEV);
+        if (int rc = slot_wait(s))
+            return rc;
         const size_t cnt = j - i;
         /* slice-local descriptors keep the same relative 16-byte alignment as the caller's buffers */
         const uint64_t in_base = in.lo & ~(uint64_t)15, out_base = out.lo & ~(uint64_t)15, aad_base = ad.lo & ~(uint64_t)15;
@@ -559,22 +603,26 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
         const int lanes = choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu);
         bool aligned;
         build_chunks(s.h_recs, cnt, lanes, (unsigned)p->eng->ncu, ch, order, aligned);
-        const uint64_t mask_base = mk.lo & ~(uint64_t)15;
         if (supp != nullptr) {
+            /* the masks the kernel writes get packed places in d_mask; where they go in h_mask stays on the host */
+            if (nmask != 0)
+                if (int rc = slot_mask_buffer(p, s))
+                    return rc;
+            s.mask_host = hmask;
             for (size_t t = 0; t < cnt; ++t) {
-                s.h_supp[t] = supp[i + t];
-                if (s.h_supp[t].flags & PTLS_HIP_SUPP_ENABLE) {
-                    s.h_supp[t].sample_off -= out_base;
-                    s.h_supp[t].mask_off -= mask_base;
+                ptls_hip_supp_t &sp = s.h_supp[t] = supp[i + t];
+                if (!(sp.flags & PTLS_HIP_SUPP_ENABLE))
+                    continue;
+                sp.sample_off -= out_base;
+                if (sp.hp_key < hp_ks->nslots) {
+                    sp.mask_off = 16 * (uint64_t)s.mask_dst.size();
+                    s.mask_dst.push_back(supp[i + t].mask_off);
+                } else {
+                    sp.mask_off = 0; /* skipped by the kernel */
                 }
             }
             HIP_TRY(hipMemcpyAsync(s.d_supp, s.h_supp, cnt * sizeof(ptls_hip_supp_t), hipMemcpyHostToDevice, s.stream),
                     PTLS_HIP_ENODEV);
-            /* the mask span goes in as well (16 B per packet), so mask bytes of packets without header protection
-             * and between masks come back unchanged */
-            if (mk.hi > mk.lo)
-                HIP_TRY(hipMemcpyAsync(s.d_mask + (mk.lo - mask_base), hmask + mk.lo, mk.hi - mk.lo, hipMemcpyHostToDevice, s.stream),
-                        PTLS_HIP_ENODEV);
         }
         std::memcpy(s.h_chunks, ch.data(), ch.size() * sizeof(Chunk));
         std::memcpy(s.h_order, order.data(), cnt * sizeof(uint32_t));
@@ -666,9 +714,8 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
         for (const Span &pc : pieces)
             HIP_TRY(hipMemcpyAsync(hout + pc.lo, s.d_out + (pc.lo - out_base), pc.hi - pc.lo, hipMemcpyDeviceToHost, s.stream),
                     PTLS_HIP_ENODEV);
-        if (supp != nullptr && mk.hi > mk.lo)
-            HIP_TRY(hipMemcpyAsync(hmask + mk.lo, s.d_mask + (mk.lo - mask_base), mk.hi - mk.lo, hipMemcpyDeviceToHost, s.stream),
-                    PTLS_HIP_ENODEV);
+        if (!s.mask_dst.empty()) /* the slice's masks, packed: one copy; slot_wait places them */
+            HIP_TRY(hipMemcpyAsync(s.h_mask, s.d_mask, 16 * s.mask_dst.size(), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
         if (open) {
             /* results come back in slice order; the caller's array is indexed like recs */
             HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream),
@@ -679,11 +726,9 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
         i = j;
         ++k;
     }
-    for (auto &s : p->slot) {
-        if (s.busy)
-            HIP_TRY(hipEventSynchronize(s.done), PTLS_HIP_ENODEV);
-        s.busy = false;
-    }
+    for (auto &s : p->slot)
+        if (int rc = slot_wait(s))
+            return rc;
     return 0;
 }
 

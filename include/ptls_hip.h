@@ -350,8 +350,10 @@ int ptls_hip_tls13_open_batch(ptls_hip_batch_t *batch, ptls_hip_keyset_t *ks, co
  * store, lib/fusion.c:388-397, :632): a slice's output comes back as the records' runs, several runs
  * joined by one copy over short gaps that were first filled, on the device, with the caller's own bytes
  * of those gaps (read when the slice is planned; do not modify them during the call), never over another
- * slice's record.  The mask span of seal_supp is uploaded before and copied back after the kernel, so its
- * other bytes come back unchanged as well. */
+ * slice's record.  The masks of seal_supp are written packed into the slice's staging, come back by one
+ * copy per slice and are placed at their mask_off by the host: no other byte of h_mask is read or written,
+ * the masks of a slice may lie anywhere in h_mask (between other slices' masks too), and a slice ends
+ * after slice_bytes / 64 masks. */
 typedef struct st_ptls_hip_pipeline_t ptls_hip_pipeline_t;
 ptls_hip_pipeline_t *ptls_hip_pipeline_new(ptls_hip_engine_t *engine, size_t slice_bytes);
 void ptls_hip_pipeline_free(ptls_hip_pipeline_t *p);
