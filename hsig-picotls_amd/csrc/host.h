@@ -6,6 +6,8 @@
  *   keyset.cpp         keysets: AES key slots + GHASH basis, or ChaCha key slots; keys / IVs / TLS 1.3 secrets
  *   planner.cpp        the launch planner: lanes per record, chunks, grid
  *   batch.cpp          batches and the device-resident seal / open / header-protection calls
+ *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls
+ *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   pipeline.cpp       host-resident records: the mapped and copy transports
  *   node.cpp           one batch over several devices, NUMA placement

@@ -213,6 +213,26 @@ int launch_chacha_mask(const ptls_hip_supp_t *supp, uint32_t n, const uint8_t *s
 int launch_chacha_keysetup(ChaChaSlot *slots, const uint8_t *keys, const uint8_t *ivs, uint32_t first, uint32_t count,
                            void *stream);
 
+/* ---- QUIC header protection around the record kernels (quic_kernel.hip) ---- */
+
+struct QuicArgs {
+    const ptls_hip_quic_packet_t *pkts; /* caller order */
+    uint32_t n;
+    const uint32_t *order;       /* plan position -> packet index of the inner batch's plan; nullptr: the identity */
+    ptls_hip_record_t *recs;     /* the inner batch's descriptors, caller order: written */
+    ptls_hip_record_t *recs_ord; /* the same in plan order, when the plan has one (else nullptr): written */
+    uint8_t *pkt;
+    uint64_t *pn_out;
+    const KeySlot *hp_slots;     /* AES header protection */
+    const ChaChaSlot *hp_chacha; /* ChaCha20 header protection */
+    const uint32_t *t0;          /* AES T0 table (AES only) */
+};
+
+/* rounds: 10 / 14 (AES-128 / AES-256 header protection) or 0 (ChaCha20) */
+int launch_quic_unprotect(int rounds, const QuicArgs &a, unsigned grid, void *stream);
+int launch_quic_protect(const ptls_hip_quic_packet_t *pkts, uint32_t n, uint8_t *pkt, const uint8_t *mask, unsigned grid,
+                        void *stream);
+
 } // namespace ptls_hip
 
 #endif

@@ -29,6 +29,10 @@ TLS13_DECODE_ERROR = -50
 TLS13_SHORT_RECORD = -20  # a complete application-data record shorter than a tag (PTLS_ALERT_BAD_RECORD_MAC)
 TRANSPORT_AUTO, TRANSPORT_COPY, TRANSPORT_MAPPED = 0, 1, 2
 ALGO_AESGCM, ALGO_CHACHA20POLY1305 = 1, 2
+QUIC_PACKET_DTYPE = np.dtype([("pkt_off", "<u8"), ("data_off", "<u8"), ("pn", "<u8"), ("pkt_len", "<u4"), ("key", "<u4"),
+                              ("hp_key", "<u4"), ("pn_offset", "<u2"), ("pn_len", "u1"), ("flags", "u1")])
+assert QUIC_PACKET_DTYPE.itemsize == 40
+QUIC_UNPROTECTED = 1
 EINVAL = -1
 
 
@@ -79,6 +83,11 @@ SIGNATURES = {
     "ptls_hip_chacha20_mask_batch": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ptls_hip_batch_set_chacha_lanes": (_i, [_vp, _i]),
     "ptls_hip_batch_chacha_lanes": (_i, [_vp]),
+    "ptls_hip_quic_batch_new": (_vp, [_vp, _vp, _sz, _i, _vp]),
+    "ptls_hip_quic_batch_free": (None, [_vp]),
+    "ptls_hip_quic_batch_records": (_vp, [_vp]),
+    "ptls_hip_quic_seal_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_quic_open_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -363,6 +372,54 @@ class Batch:
     def close(self):
         if self.ptr:
             lib().ptls_hip_batch_free(self.ptr)
+            self.ptr = None
+
+
+class _BorrowedBatch(Batch):
+    """the inner record batch of a QuicBatch: owned and freed by it"""
+
+    def __init__(self, engine, ptr):  # pylint: disable=super-init-not-called
+        self.engine, self.recs, self.ptr = engine, None, ptr
+
+    def __len__(self):
+        return lib().ptls_hip_batch_count(self.ptr)
+
+    def close(self):
+        self.ptr = None
+
+
+class QuicBatch:
+    """QUIC packet protection with the packets on the device (ptls_hip_quic_*): pkts = QUIC_PACKET_DTYPE descriptors, planned
+    for seal (open=False) or open (open=True).  Calls on one QuicBatch must be ordered (same stream)."""
+
+    def __init__(self, engine, pkts, open=False, stream=None):  # noqa: A002
+        pkts = np.ascontiguousarray(pkts, dtype=QUIC_PACKET_DTYPE)
+        self.engine, self.pkts, self.is_open = engine, pkts, bool(open)
+        self.ptr = lib().ptls_hip_quic_batch_new(engine.ptr, pkts.ctypes.data, len(pkts), int(self.is_open), _stream(stream))
+        if not self.ptr:
+            raise HipError(f"ptls_hip_quic_batch_new: {last_error()}")
+
+    def __len__(self):
+        return len(self.pkts)
+
+    def records(self):
+        """the inner record batch (borrowed): set_lanes / set_chacha_lanes / set_max_workgroups work on it"""
+        return _BorrowedBatch(self.engine, lib().ptls_hip_quic_batch_records(self.ptr))
+
+    def seal(self, keyset, hp_keyset, inp, pkt, stream=None):
+        """payloads at inp + data_off -> protected packets at pkt + pkt_off (the unprotected headers are already there)"""
+        _check(lib().ptls_hip_quic_seal_batch(self.ptr, keyset.ptr, hp_keyset.ptr, _ptr(inp), _ptr(pkt), _stream(stream)),
+               "quic_seal_batch")
+
+    def open(self, keyset, hp_keyset, pkt, out, result, pn_out, stream=None):
+        """unprotects the headers in pkt, decodes the packet numbers into pn_out, opens the payloads into out + data_off;
+        result[i] = payload length or UINT64_MAX"""
+        _check(lib().ptls_hip_quic_open_batch(self.ptr, keyset.ptr, hp_keyset.ptr, _ptr(pkt), _ptr(out), _ptr(result),
+                                              _ptr(pn_out), _stream(stream)), "quic_open_batch")
+
+    def close(self):
+        if self.ptr:
+            lib().ptls_hip_quic_batch_free(self.ptr)
             self.ptr = None
 
 

@@ -432,6 +432,73 @@ void ptls_hip_node_host_free(void *ptr, size_t bytes);
 size_t ptls_hip_host_page_nodes(const void *ptr, size_t bytes, size_t stride, int *nodes, size_t cap);
 
 /* ------------------------------------------------------------------------------------------ *
+ * 2e. QUIC packet protection (RFC 9001 §5.3, §5.4) over the same batches, packets on the device  *
+ * ------------------------------------------------------------------------------------------ */
+
+/* One QUIC packet (40 bytes).  Offsets are byte offsets into the buffers passed to the calls below; packets may lie at
+ * any byte offset.  The packet is header (pn_offset bytes) || packet number (pn_len bytes) || payload || 16-byte tag. */
+typedef struct st_ptls_hip_quic_packet_t {
+    uint64_t pkt_off;   /* first header byte of the packet in `pkt` */
+    uint64_t data_off;  /* seal: the plaintext payload in `in`; open: where the plaintext goes in `out` */
+    uint64_t pn;        /* seal: the full packet number (< 2^62);
+                           open: the expected one = largest packet number received in this space + 1 */
+    uint32_t pkt_len;   /* whole packet: header, packet number, payload, 16-byte tag */
+    uint32_t key;       /* AEAD key slot */
+    uint32_t hp_key;    /* header-protection key slot */
+    uint16_t pn_offset; /* header bytes in front of the packet-number field (>= 1) */
+    uint8_t pn_len;     /* seal: 1..4, equal to (first byte & 3) + 1 of the header the caller wrote; open: ignored */
+    uint8_t flags;      /* open: PTLS_HIP_QUIC_UNPROTECTED = the header is already unprotected (see below) */
+} ptls_hip_quic_packet_t;
+#define PTLS_HIP_QUIC_UNPROTECTED 1u
+
+/* A QUIC batch: `n` host descriptors uploaded and planned for seal (open == 0) or for open (open != 0); reusable for any
+ * number of calls of that direction over same-shaped buffers.  NULL (PTLS_HIP_EINVAL in ptls_hip_last_error, which names
+ * the packet's index) when a packet has pn_offset == 0 or pkt_len < pn_offset + 4 + 16 (its header-protection sample would
+ * leave the packet: a QUIC stack drops such packets before decryption), or for seal pn_len outside 1..4 or pn >= 2^62.
+ * n == 0 makes a batch whose calls succeed and launch nothing.
+ * quic_batch_records: the inner record batch, borrowed (freed with the QUIC batch): ptls_hip_batch_set_lanes,
+ * _set_chacha_lanes and _set_max_workgroups work on it as on any batch. */
+typedef struct st_ptls_hip_quic_batch_t ptls_hip_quic_batch_t;
+ptls_hip_quic_batch_t *ptls_hip_quic_batch_new(ptls_hip_engine_t *engine, const ptls_hip_quic_packet_t *pkts, size_t n, int open,
+                                               void *stream);
+void ptls_hip_quic_batch_free(ptls_hip_quic_batch_t *batch);
+ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *batch);
+
+/* Both calls: all buffers are device memory, the call is asynchronous on `stream`, the cipher (AES-128-GCM, AES-256-GCM or
+ * ChaCha20-Poly1305) is the keyset's (ptls_hip_keyset_algo), and hp_ks must be of the same algorithm and key size, as for
+ * seal_batch_supp.  PTLS_HIP_EINVAL, nothing launched, for a key or hp_key outside its keyset (the message names the
+ * packet), keysets of different algorithms or key sizes, a seal batch passed to open or an open batch passed to seal, or
+ * a null buffer.
+ *
+ * seal: the caller has written the unprotected header (pn_offset + pn_len bytes, the truncated packet number included) at
+ * pkt + pkt_off.  The call seals the pkt_len - pn_offset - pn_len - 16 payload bytes at in + data_off (AAD = that header,
+ * nonce from pn) into the packet right after the header, takes the 16-byte sample at pn_offset + 4 and protects the header
+ * in place (RFC 9001 §5.4.1: first byte ^= mask[0] & 0x0f for a long header, & 0x1f for a short one; packet-number byte j
+ * ^= mask[1 + j]).  `in` may be `pkt` itself with data_off = pkt_off + pn_offset + pn_len.  Exactly the packet's pkt_len
+ * bytes change in `pkt`.
+ *
+ * open: unless PTLS_HIP_QUIC_UNPROTECTED is set, the mask is computed from the sample and removed from the first byte,
+ * pn_len = (first & 3) + 1 is read, that many packet-number bytes are unmasked, and those 1 + pn_len bytes are written back
+ * into `pkt` (nothing else in `pkt` is written: the caller can then read the key phase and the reserved bits).  With the
+ * flag, pn_len is read from the first byte as it stands.  The full packet number, decoded from the truncated one and the
+ * expected `pn` as in RFC 9000 Appendix A.3, goes to pn_out[i].  The record is then opened as by the open_batch calls:
+ * AAD = the unprotected header, plaintext to out + data_off (written even on failure), result[i] = payload length or
+ * UINT64_MAX on authentication failure.  `out` must not overlap `pkt`.  A packet that fails under one key can be
+ * re-submitted under another (the next key phase) with the flag set.
+ *
+ * Ordering: an open call rewrites the batch's device descriptors (record length, AAD length, input offset and nonce are
+ * known only once the header is unprotected), and the seal call's masks pass through a buffer of the batch.  Calls on one
+ * QUIC batch must therefore be ordered: on the same stream, or by the caller's own synchronisation.
+ *
+ * Out of scope: the host pipelines (2c) and the node API (2d); splitting coalesced datagrams and parsing long-header fields
+ * (the caller supplies pn_offset); Retry and Version Negotiation packets (they carry no packet protection); choosing the
+ * key by key phase on the device (the AES planner needs every packet's key slot on the host). */
+int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
+                             void *pkt, void *stream);
+int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, void *pkt, void *out,
+                             uint64_t *result, uint64_t *pn_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
  *    seeded with seed ^ g(i), written at buf + recs[i].in_off for recs[i].len     *
  *    bytes, where g(i) = index[i] if `index` (device array of n uint64) is given, else base + i.     *
