@@ -181,7 +181,6 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
         return fail(PTLS_HIP_EINVAL, "seal/open: null buffer");
     DeviceGuard g(b->eng->device);
     const uint8_t *in8 = static_cast<const uint8_t *>(in), *aad8 = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
-    const uint32_t hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
     const bool aligned = b->all_aligned && ((reinterpret_cast<uintptr_t>(in8) | reinterpret_cast<uintptr_t>(aad8) |
                                              reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     int e;
@@ -196,7 +195,7 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
         a.slots = ks->d_chacha;
         a.supp = supp;
         a.hp_slots = hp_ks != nullptr ? hp_ks->d_chacha : nullptr;
-        a.hp_nslots = hp_nslots;
+        a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
         a.mask = static_cast<uint8_t *>(mask);
         e = launch_chacha_batch(b->chacha_lanes, open, stream, a, aligned);
     } else {
@@ -210,12 +209,8 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
         a.aad = aad8;
         a.out = static_cast<uint8_t *>(out);
         a.result = result;
-        a.slots = ks->d_slots;
-        a.basis = ks->d_basis;
-        a.t0 = b->eng->d_t0;
+        set_key_args(a, b->eng, ks, hp_ks);
         a.supp = supp;
-        a.hp_slots = hp_ks != nullptr ? hp_ks->d_slots : nullptr;
-        a.hp_nslots = hp_nslots;
         a.mask = static_cast<uint8_t *>(mask);
         const unsigned grid = plan_grid(b->n, b->nchunks, b->lanes, batch_cus(b));
         if (b->d_clk != nullptr && b->clk_bytes < (size_t)grid * 32)
@@ -287,7 +282,7 @@ static int mask_batch(const char *who, int algo, ptls_hip_engine_t *eng, ptls_hi
     if (n == 0)
         return 0;
     DeviceGuard g(eng->device);
-    const unsigned grid = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)eng->ncu * 4);
+    const unsigned grid = record_grid(n, eng->ncu);
     const uint8_t *src8 = static_cast<const uint8_t *>(src);
     uint8_t *mask8 = static_cast<uint8_t *>(mask);
     const int e = chacha ? launch_chacha_mask(supp, (uint32_t)n, src8, mask8, hp_ks->d_chacha, (uint32_t)hp_ks->nslots, grid, stream)

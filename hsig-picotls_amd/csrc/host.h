@@ -9,7 +9,8 @@
  *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
- *   pipeline.cpp       host-resident records: the mapped and copy transports
+ *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places (no HIP call)
+ *   pipeline.cpp       host-resident records: the mapped and copy transports over one slice launcher (launch_slice)
  *   node.cpp           one batch over several devices, NUMA placement
  *   plugin_worker.cpp  the picotls plugin's runtime: the resident worker dispatch and pooled resources
  *   plugin.cpp         the picotls plugin objects (AEAD, CTR, ECB, fusion-style low-level API)
@@ -159,6 +160,24 @@ inline unsigned batch_cus(const st_ptls_hip_batch_t *b)
     return b->max_wg != 0 && b->max_wg < ncu ? b->max_wg : ncu;
 }
 
+/* the grid of the one-thread-per-record kernels (TLS 1.3 headers / inner plaintext, stand-alone masks): 256 threads per
+ * workgroup, at most four workgroups per CU */
+inline unsigned record_grid(size_t n, int ncu)
+{
+    const size_t wgs = (n + 255) / 256, cap = (size_t)ncu * 4;
+    return (unsigned)(wgs < cap ? wgs : cap);
+}
+
+/* the key material of an AES-GCM launch: the keyset's slots and basis, the engine's T-table, the header-protection slots */
+inline void set_key_args(KernelArgs &a, const ptls_hip_engine_t *eng, const ptls_hip_keyset_t *ks, const ptls_hip_keyset_t *hp_ks)
+{
+    a.slots = ks->d_slots;
+    a.basis = ks->d_basis;
+    a.t0 = eng->d_t0;
+    a.hp_slots = hp_ks != nullptr ? hp_ks->d_slots : nullptr;
+    a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
+}
+
 class DeviceGuard {
   public:
     explicit DeviceGuard(int dev)
@@ -199,6 +218,66 @@ int plan_wg(const std::vector<Chunk> &ch, int lanes);
 void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned ncu, std::vector<Chunk> &ch,
                   std::vector<uint32_t> &order, bool &all_aligned);
 bool identity_order(const std::vector<uint32_t> &order, size_t n);
+
+/* ---- slice_plan.cpp: what the copy transport places where, per slice (arithmetic on descriptors, no HIP call) ---- */
+/* what a pipeline slice runs: plain seal / open (AAD in its own buffer), or the TLS 1.3 record layer
+ * (seal: the 5-byte headers are written into the output and read back as the AAD, like
+ * ptls_hip_tls13_seal_batch; open: the AAD is the header in the received input, and the inner plaintext
+ * is parsed after the open, like ptls_hip_tls13_open_batch) */
+enum PipeMode { PIPE_SEAL, PIPE_OPEN, PIPE_TLS13_SEAL, PIPE_TLS13_OPEN };
+
+/* what the mode means for the buffers: which side carries the tag, and the buffer the AAD lives in */
+struct ModeInfo {
+    bool open;
+    bool aad_in_out, aad_in_in; /* the AAD is the header in the output (TLS 1.3 seal) / in the input (TLS 1.3 open) */
+    uint32_t tag_in, tag_out;   /* tag bytes after a record's input / output */
+    ModeInfo(PipeMode m)
+        : open(m == PIPE_OPEN || m == PIPE_TLS13_OPEN), aad_in_out(m == PIPE_TLS13_SEAL), aad_in_in(m == PIPE_TLS13_OPEN),
+          tag_in(open ? 16 : 0), tag_out(open ? 0 : 16)
+    {
+    }
+};
+
+/* byte range [lo, hi) */
+struct Span {
+    uint64_t lo, hi;
+};
+
+constexpr size_t COPY_DIRECT_RUNS = 8;   /* at most this many runs per slice: one copy each, no gap is written */
+constexpr uint64_t GAP_SPLIT = 64 << 10; /* a gap this long splits the copy instead of being filled */
+/* masks per slice: the slot's d_mask holds slice_bytes / 4 */
+constexpr size_t slot_max_masks(size_t slice_bytes)
+{
+    return slice_bytes / 64;
+}
+
+/* per call: the records are in output order (each record's output starts at or after the previous one's end, the usual
+ * layout), so a slice's gaps hold no other slice's bytes; otherwise `uni`, the merged union of every record's output,
+ * decides that */
+struct CopyOrder {
+    bool in_order;
+    std::vector<Span> uni;
+};
+void plan_copy_order(const ptls_hip_record_t *recs, size_t n, const ModeInfo &m, CopyOrder &o);
+
+/* per slice: records [i, j) and everything the host places for them */
+struct SlicePlan {
+    size_t j;
+    Span in, out, aad;                    /* the bytes of the caller's buffers the slice stages (aad: {0, 0} if none) */
+    uint64_t in_base, out_base, aad_base; /* what the slice-local offsets are relative to: the span starts, rounded down to 16 */
+    std::vector<ptls_hip_record_t> recs;  /* slice-local descriptors */
+    std::vector<ptls_hip_supp_t> supp;    /* ... and header-protection descriptors (empty without supp) */
+    std::vector<Span> pieces;             /* the D2H copies of the output, in the caller's offsets */
+    std::vector<GapPiece> gaps;           /* the gaps inside the pieces, filled in the staging before the kernels run ... */
+    std::vector<Span> gap_src;            /* ... with these bytes of the caller's output */
+    std::vector<uint64_t> mask_dst;       /* the caller's mask_off of the t-th mask the kernel writes (local mask_off 16 t) */
+    std::vector<Span> runs;               /* scratch: the records' merged output runs */
+};
+/* the greedy cut from record i against the staging limits (slice_bytes of input and output, slice_bytes / 4 of AAD,
+ * slot_max_masks masks, max_recs - 1 records), then the slice's plan; EINVAL for a record that does not fit a slice or a
+ * header-protection sample outside the slice's output */
+int plan_copy_slice(const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, size_t n, size_t i, const ModeInfo &m,
+                    size_t slice_bytes, size_t max_recs, size_t hp_nslots, const CopyOrder &o, SlicePlan &pl);
 
 /* ---- batch.cpp ---- */
 /* one asynchronous seal / open launch of a planned batch (the device-resident calls and the TLS 1.3 ones), with the

@@ -1017,8 +1017,9 @@ __global__ void __launch_bounds__(WORKER_WG)
                     }
                     if (seq == last && (quit != 0 || now - t_last > idle_ticks || now - t_start > life_ticks))
                         leave = true;
-                    /* no new read once a request is seen: the acquire below waits for every read still in flight, and
-                     * one issued now would add a whole PCIe round trip (round 6) */
+                    /* reads keep being issued, also on the iteration that sees a request: the acquire below drains every
+                     * read still in flight.  (Not re-issuing once a request is seen was measured slower and rejected:
+                     * profiles/r06_plugin/plugin_ab_wave1_noreissue.log.) */
                     ring[k] = poll_word(ms);
                     __builtin_amdgcn_s_sleep(2);
                 }

@@ -57,7 +57,7 @@ extern "C" int ptls_hip_tls13_seal_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t 
     if (b->n == 0)
         return 0;
     DeviceGuard g(b->eng->device);
-    const unsigned grid = (unsigned)std::min<size_t>((b->n + 255) / 256, (size_t)b->eng->ncu * 4);
+    const unsigned grid = record_grid(b->n, b->eng->ncu);
     const int e = launch_tls13_headers(b->d_recs, (uint32_t)b->n, static_cast<uint8_t *>(out), grid, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "tls13_seal_batch: header kernel launch failed: %s", hipGetErrorString((hipError_t)e));
@@ -133,7 +133,7 @@ extern "C" int ptls_hip_tls13_open_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t 
     if (rc != 0 || b->n == 0)
         return rc;
     DeviceGuard g(b->eng->device);
-    const unsigned grid = (unsigned)std::min<size_t>((b->n + 255) / 256, (size_t)b->eng->ncu * 4);
+    const unsigned grid = record_grid(b->n, b->eng->ncu);
     const int e = launch_tls13_inner(b->d_recs, (uint32_t)b->n, static_cast<const uint8_t *>(out), result, grid, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "tls13_open_batch: inner-plaintext kernel launch failed: %s", hipGetErrorString((hipError_t)e));

@@ -11,6 +11,10 @@
  *   - the launch planner (choose_lanes / build_chunks / plan_grid) on random descriptor sets, every plan checked to be a
  *     permutation in key runs;
  *   - ptls_hip_partition_bytes on random lengths and part counts;
+ *   - the copy transport's slice plans (plan_copy_order / plan_copy_slice, slice_plan.cpp) on a thousand random layouts --
+ *     the four modes, records in and out of output order, with and without header-protection descriptors in three mask
+ *     layouts, 64 KiB and 1 MiB slices -- every slice's cut, spans, descriptors, copies back, gaps and mask places
+ *     checked against the layout, and the two refusals;
  *   - the argument checks of the C ABI with NULL / out-of-range arguments, and the plugin's setup_crypto without a device
  *     (it must fail cleanly: no CPU fallback);
  *   - with a gfx950 device (argument "device", run on the GPU box): the host pipelines over random layouts -- both
@@ -233,6 +237,292 @@ static void check_partition(std::mt19937_64 &rng, int sets)
     CHECK(ptls_hip_partition_bytes(nullptr, 0, 0, b) == PTLS_HIP_EINVAL);
 }
 
+/* ---- the copy transport's slice plans (slice_plan.cpp): what the host places where ---- */
+
+/* a random record list like pipeline_trial's: records of 0-2 000 bytes, 1-64-byte gaps in the output (`holes`: now and
+ * then one of GAP_SPLIT or more), in output order or shuffled, the AAD where the mode keeps it */
+struct Layout {
+    std::vector<ptls_hip_record_t> recs;
+    std::vector<ptls_hip_supp_t> supp;
+    uint64_t out_sz;
+};
+
+static Layout random_layout(std::mt19937_64 &rng, size_t n, PipeMode mode, bool shuffled, bool holes, int mask_layout, size_t hp_nslots,
+                            uint32_t max_len = 2000)
+{
+    const ModeInfo m(mode);
+    Layout L;
+    L.recs.resize(n);
+    uint64_t in = 0, out = 0, aad = 0;
+    for (size_t i = 0; i < n; ++i) {
+        ptls_hip_record_t &r = L.recs[i] = ptls_hip_record_t{};
+        r.len = (uint32_t)(rng() % (max_len + 1));
+        r.seq = 1000 + i;
+        r.key = (uint32_t)((i * 3) / n);
+        in += rng() % 4;
+        out += 1 + rng() % 64 + (holes && rng() % 50 == 0 ? GAP_SPLIT + rng() % 4096 : 0);
+        if (m.aad_in_out || m.aad_in_in) { /* the 5-byte header in front of the record, on the wire side */
+            uint64_t &wire = m.aad_in_out ? out : in;
+            r.aad_off = wire;
+            r.aad_len = 5;
+            wire += 5;
+        } else {
+            r.aad_off = aad + rng() % 4;
+            r.aad_len = (uint32_t)(rng() % 41);
+            aad = r.aad_off + r.aad_len;
+        }
+        r.in_off = in;
+        r.out_off = out;
+        in += r.len + m.tag_in;
+        out += r.len + m.tag_out;
+    }
+    L.out_sz = out + 1 + rng() % 64;
+    if (mask_layout >= 0) { /* masks packed in record order / packed in reverse / strided at odd offsets */
+        L.supp.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            ptls_hip_supp_t &sp = L.supp[i] = ptls_hip_supp_t{};
+            sp.flags = rng() % 4 != 0 ? PTLS_HIP_SUPP_ENABLE : 0;
+            sp.hp_key = (uint32_t)(rng() % (hp_nslots + 2)); /* some outside the keyset: skipped by the kernel */
+            sp.sample_off = L.recs[i].out_off + rng() % (L.recs[i].len + 1);
+            sp.mask_off = mask_layout == 0 ? 16 * i : mask_layout == 1 ? 16 * (n - 1 - i) : 48 * i + 7;
+        }
+    }
+    if (shuffled) {
+        std::vector<size_t> perm(n);
+        for (size_t i = 0; i < n; ++i)
+            perm[i] = i;
+        std::shuffle(perm.begin(), perm.end(), rng);
+        Layout S = L;
+        for (size_t k = 0; k < n; ++k) {
+            S.recs[k] = L.recs[perm[k]];
+            if (!L.supp.empty())
+                S.supp[k] = L.supp[perm[k]];
+        }
+        return S;
+    }
+    return L;
+}
+
+/* the output byte ranges of a record, from the mode's definition */
+static std::vector<Span> out_parts(const ptls_hip_record_t &r, const ModeInfo &m)
+{
+    std::vector<Span> v;
+    if (m.aad_in_out && r.aad_len != 0)
+        v.push_back(Span{r.aad_off, r.aad_off + r.aad_len});
+    if (r.len + m.tag_out != 0)
+        v.push_back(Span{r.out_off, r.out_off + r.len + m.tag_out});
+    return v;
+}
+
+/* the spans records [a, b) need in the input, output and AAD staging */
+static void staged_spans(const std::vector<ptls_hip_record_t> &recs, size_t a, size_t b, const ModeInfo &m, Span &in, Span &out, Span &ad)
+{
+    in = out = ad = Span{UINT64_MAX, 0};
+    auto add = [](Span &s, uint64_t lo, uint64_t hi) { s = Span{std::min(s.lo, lo), std::max(s.hi, hi)}; };
+    for (size_t t = a; t < b; ++t) {
+        const ptls_hip_record_t &r = recs[t];
+        add(in, r.in_off, r.in_off + r.len + m.tag_in);
+        add(out, r.out_off, r.out_off + r.len + m.tag_out);
+        add(m.aad_in_out ? out : m.aad_in_in ? in : ad, r.aad_off, r.aad_off + r.aad_len);
+    }
+}
+
+static bool writes_a_mask(const ptls_hip_supp_t &sp, size_t hp_nslots)
+{
+    return (sp.flags & PTLS_HIP_SUPP_ENABLE) && sp.hp_key < hp_nslots;
+}
+
+/* plans every slice of the layout and checks the eight properties of a plan (numbered as in the comments) */
+static void check_layout_plans(const Layout &L, PipeMode mode, size_t slice_bytes, size_t hp_nslots)
+{
+    const ModeInfo m(mode);
+    const std::vector<ptls_hip_record_t> &recs = L.recs;
+    const ptls_hip_supp_t *supp = L.supp.empty() ? nullptr : L.supp.data();
+    const size_t n = recs.size(), max_recs = slice_bytes / 16 + 1;
+    CopyOrder ord;
+    plan_copy_order(recs.data(), n, m, ord);
+    std::vector<SlicePlan> plans;
+    std::vector<size_t> first;
+    /* owner[b]: 1 + the slice whose record writes output byte b (the layout's records do not overlap), 0: a gap */
+    std::vector<uint32_t> owner(L.out_sz, 0);
+    for (size_t i = 0; i < n;) {
+        SlicePlan pl;
+        const int rc = plan_copy_slice(recs.data(), supp, n, i, m, slice_bytes, max_recs, hp_nslots, ord, pl);
+        CHECK(rc == 0);
+        /* 1. the slices partition [0, n) in order and none is empty */
+        CHECK(rc == 0 && pl.j > i && pl.j <= n);
+        if (rc != 0 || pl.j <= i || pl.j > n)
+            return;
+        const size_t j = pl.j, cnt = j - i;
+        /* 2. the staged spans are the records', and within the limits */
+        Span in, out, ad;
+        staged_spans(recs, i, j, m, in, out, ad);
+        CHECK(pl.in.lo == in.lo && pl.in.hi == in.hi && pl.out.lo == out.lo && pl.out.hi == out.hi);
+        CHECK(ad.hi > ad.lo ? pl.aad.lo == ad.lo && pl.aad.hi == ad.hi : pl.aad.lo == 0 && pl.aad.hi == 0);
+        CHECK(pl.in.hi - pl.in.lo <= slice_bytes && pl.out.hi - pl.out.lo <= slice_bytes && pl.aad.hi - pl.aad.lo <= slice_bytes / 4);
+        size_t nmask = 0;
+        for (size_t t = i; supp != nullptr && t < j; ++t)
+            nmask += writes_a_mask(supp[t], hp_nslots);
+        CHECK(nmask <= slice_bytes / 64 && pl.mask_dst.size() == nmask && cnt <= max_recs - 1);
+        /* 3. the cut is the greedy one: the next record would break a limit */
+        if (j < n) {
+            staged_spans(recs, i, j + 1, m, in, out, ad);
+            CHECK(cnt == max_recs - 1 || (supp != nullptr && writes_a_mask(supp[j], hp_nslots) && nmask == slice_bytes / 64) ||
+                  in.hi - in.lo > slice_bytes || out.hi - out.lo > slice_bytes || (ad.hi > ad.lo && ad.hi - ad.lo > slice_bytes / 4));
+        }
+        /* 6. the slice-local descriptors are the caller's minus the bases, and the bases keep the alignment */
+        CHECK(pl.in_base % 16 == 0 && pl.out_base % 16 == 0 && pl.aad_base % 16 == 0);
+        CHECK(pl.in_base <= pl.in.lo && pl.in.lo - pl.in_base < 16 && pl.out_base <= pl.out.lo && pl.out.lo - pl.out_base < 16 &&
+              pl.aad_base <= pl.aad.lo && pl.aad.lo - pl.aad_base < 16);
+        CHECK(pl.recs.size() == cnt && pl.supp.size() == (supp != nullptr ? cnt : 0));
+        for (size_t t = 0; t < cnt && t < pl.recs.size(); ++t) {
+            const ptls_hip_record_t &a = pl.recs[t], &b = recs[i + t];
+            CHECK(a.in_off + pl.in_base == b.in_off && a.out_off + pl.out_base == b.out_off);
+            CHECK(a.aad_off + (m.aad_in_out ? pl.out_base : m.aad_in_in ? pl.in_base : pl.aad_base) == b.aad_off);
+            CHECK(a.seq == b.seq && a.len == b.len && a.aad_len == b.aad_len && a.key == b.key && a.flags == b.flags);
+        }
+        /* 7. the mask places: in record order, exactly the masks the kernel writes, packed 16 bytes apart */
+        for (size_t t = 0, k = 0; t < pl.supp.size(); ++t) {
+            const ptls_hip_supp_t &a = pl.supp[t], &b = supp[i + t];
+            CHECK(a.flags == b.flags && a.hp_key == b.hp_key);
+            if (!(b.flags & PTLS_HIP_SUPP_ENABLE)) {
+                CHECK(a.sample_off == b.sample_off && a.mask_off == b.mask_off);
+                continue;
+            }
+            CHECK(a.sample_off + pl.out_base == b.sample_off);
+            if (writes_a_mask(b, hp_nslots)) {
+                CHECK(k < pl.mask_dst.size() && pl.mask_dst[k] == b.mask_off && a.mask_off == 16 * k);
+                ++k;
+            }
+        }
+        for (size_t t = i; t < j; ++t)
+            for (const Span &s : out_parts(recs[t], m))
+                std::fill(owner.begin() + s.lo, owner.begin() + s.hi, (uint32_t)plans.size() + 1);
+        first.push_back(i);
+        plans.push_back(std::move(pl));
+        i = j;
+    }
+    std::vector<uint8_t> gapmark(L.out_sz, 0);
+    for (size_t k = 0; k < plans.size(); ++k) {
+        const SlicePlan &pl = plans[k];
+        /* the slice's runs: its records' output parts, merged where they touch */
+        std::vector<Span> parts;
+        uint64_t part_bytes = 0, gap_bytes = 0;
+        for (size_t t = first[k]; t < pl.j; ++t)
+            for (const Span &s : out_parts(recs[t], m)) {
+                parts.push_back(s);
+                part_bytes += s.hi - s.lo;
+            }
+        std::sort(parts.begin(), parts.end(), [](const Span &a, const Span &b) { return a.lo < b.lo; });
+        size_t nruns = 0;
+        for (size_t t = 0; t < parts.size(); ++t)
+            nruns += t == 0 || parts[t].lo > parts[t - 1].hi;
+        /* 5. every gap: short, no record's output (this slice's or another's), none at all with few runs, sources packed */
+        CHECK(pl.gaps.size() == pl.gap_src.size() && (nruns > COPY_DIRECT_RUNS || pl.gaps.empty()));
+        CHECK(pl.pieces.size() + pl.gaps.size() == nruns);
+        for (size_t t = 0; t < pl.gaps.size() && t < pl.gap_src.size(); ++t) {
+            const GapPiece &g = pl.gaps[t];
+            const Span &src = pl.gap_src[t];
+            CHECK(g.len != 0 && g.len < GAP_SPLIT && g.src == gap_bytes && g.dst + pl.out_base == src.lo && src.hi - src.lo == g.len);
+            CHECK(src.lo >= pl.out.lo && src.hi <= pl.out.hi);
+            for (uint64_t b = src.lo; b < src.hi && b < L.out_sz; ++b) {
+                CHECK(owner[b] == 0 && gapmark[b] == 0);
+                gapmark[b] = 1;
+            }
+            gap_bytes += g.len;
+        }
+        /* 4. the pieces: sorted, disjoint, inside the out span; they cover every output part, and beyond those the gaps */
+        uint64_t seen_parts = 0, seen_gaps = 0;
+        for (size_t t = 0; t < pl.pieces.size(); ++t) {
+            const Span &pc = pl.pieces[t];
+            CHECK(pc.lo < pc.hi && pc.lo >= pl.out.lo && pc.hi <= pl.out.hi && (t == 0 || pc.lo > pl.pieces[t - 1].hi));
+            for (uint64_t b = pc.lo; b < pc.hi && b < L.out_sz; ++b) {
+                CHECK(owner[b] == k + 1 || gapmark[b] == 1);
+                seen_parts += owner[b] == k + 1;
+                seen_gaps += gapmark[b];
+            }
+            /* the copy splits only where it must: few runs, a long gap, or another slice's record in the gap */
+            if (t != 0 && nruns > COPY_DIRECT_RUNS && pc.lo - pl.pieces[t - 1].hi < GAP_SPLIT) {
+                bool other = false;
+                for (uint64_t b = pl.pieces[t - 1].hi; b < pc.lo; ++b)
+                    other = other || owner[b] != 0;
+                CHECK(other);
+            }
+        }
+        CHECK(seen_parts == part_bytes && seen_gaps == gap_bytes);
+        for (const Span &src : pl.gap_src)
+            std::fill(gapmark.begin() + std::min<uint64_t>(src.lo, L.out_sz), gapmark.begin() + std::min<uint64_t>(src.hi, L.out_sz), 0);
+    }
+}
+
+/* 8. the two refusals, with the offending record in the first slice and in a later one */
+static void check_plan_refusals(void)
+{
+    const size_t slice = 64 << 10, max_recs = slice / 16 + 1;
+    CopyOrder ord;
+    SlicePlan pl;
+    for (size_t bad : {(size_t)0, (size_t)2}) {
+        /* three 40 000-byte records, one slice each; record `bad` is larger than a slice */
+        std::vector<ptls_hip_record_t> recs(3, ptls_hip_record_t{});
+        uint64_t in = 0, out = 0;
+        for (size_t t = 0; t < 3; ++t) {
+            recs[t].len = t == bad ? (uint32_t)slice : 40000;
+            recs[t].in_off = in;
+            recs[t].out_off = out;
+            in += recs[t].len;
+            out += recs[t].len + 16;
+        }
+        plan_copy_order(recs.data(), 3, PIPE_SEAL, ord);
+        for (size_t i = 0; i < 3; ++i) {
+            const int rc = plan_copy_slice(recs.data(), nullptr, 3, i, PIPE_SEAL, slice, max_recs, 0, ord, pl);
+            if (i == bad) {
+                CHECK(rc == PTLS_HIP_EINVAL && std::strstr(ptls_hip_last_error(), "does not fit a 65536-byte slice") != nullptr);
+                break;
+            }
+            CHECK(rc == 0 && pl.j == i + 1);
+        }
+        /* the same list with every record fitting, and the sample of record `bad` outside its slice's output */
+        recs[bad].len = 40000;
+        std::vector<ptls_hip_supp_t> supp(3, ptls_hip_supp_t{});
+        for (size_t t = 0; t < 3; ++t) {
+            recs[t].out_off = t * 40100;
+            supp[t].flags = PTLS_HIP_SUPP_ENABLE;
+            supp[t].sample_off = recs[t].out_off + (t == bad ? 40016 - 15 : 4);
+            supp[t].mask_off = 16 * t;
+        }
+        plan_copy_order(recs.data(), 3, PIPE_SEAL, ord);
+        for (size_t i = 0; i < 3; ++i) {
+            const int rc = plan_copy_slice(recs.data(), supp.data(), 3, i, PIPE_SEAL, slice, max_recs, 1, ord, pl);
+            if (i == bad) {
+                CHECK(rc == PTLS_HIP_EINVAL && std::strstr(ptls_hip_last_error(), "outside the slice's output") != nullptr);
+                break;
+            }
+            CHECK(rc == 0 && pl.j == i + 1);
+        }
+    }
+}
+
+static void check_slice_plans(std::mt19937_64 &rng, int layouts)
+{
+    static const PipeMode modes[] = {PIPE_SEAL, PIPE_OPEN, PIPE_TLS13_SEAL, PIPE_TLS13_OPEN};
+    for (int l = 0; l < layouts; ++l) {
+        const PipeMode mode = modes[l % 4];
+        const size_t n = l % 5 == 0 ? 5 : 1 + rng() % 400, hp_nslots = 1 + rng() % 3;
+        /* header-protection descriptors go with a plain seal only (pipeline_run), in three mask layouts */
+        const int mask_layout = mode == PIPE_SEAL && rng() % 4 != 0 ? (int)(rng() % 3) : -1;
+        const Layout L = random_layout(rng, n, mode, rng() % 2 != 0, rng() % 4 == 0, mask_layout, hp_nslots);
+        check_layout_plans(L, mode, l % 2 ? (size_t)1 << 20 : (size_t)64 << 10, hp_nslots);
+    }
+    /* many tiny records, each with a mask: the mask staging (slice_bytes / 64 masks) ends the slices, not the bytes */
+    Layout tiny = random_layout(rng, 6000, PIPE_SEAL, false, false, 0, 8, 8);
+    for (ptls_hip_supp_t &sp : tiny.supp) {
+        sp.flags = PTLS_HIP_SUPP_ENABLE;
+        sp.hp_key %= 8;
+    }
+    check_layout_plans(tiny, PIPE_SEAL, 64 << 10, 8);
+    check_plan_refusals();
+}
+
 /* the C ABI's argument checks and the no-device paths: each must fail with an error code and a message, never crash */
 static void check_abi_without_device(void)
 {
@@ -433,6 +723,7 @@ int main(int argc, char **argv)
     check_frame(rng, 20000 * scale);
     check_planner(rng, 300 * scale);
     check_partition(rng, 20000 * scale);
+    check_slice_plans(rng, 1000 * scale);
     check_abi_without_device();
     printf("host_check: %s (%d failed checks)\n", failures == 0 ? "ok" : "FAILED", failures);
     return failures == 0 ? 0 : 1;

@@ -5,7 +5,8 @@ its own tests with ASan + UBSan, /root/reference/.github/workflows/ci.yml:24-25)
 into asan/host_check (tests/host_check/host_check.cpp), which drives, without a GPU, every host path that reads caller
 or wire bytes: 100 000 random and damaged TLS record streams through ptls_hip_tls13_parse (each in an exactly-sized heap
 buffer, so a one-byte over-read is a report), the record framing, the launch planner on random descriptor sets, the
-byte partition, and the C ABI's argument checks and no-device paths.  A sanitizer report aborts the driver.  (The Python
+byte partition, the copy transport's slice plans (slice_plan.cpp: cut, descriptors, copies back, gaps, mask places and
+refusals on a thousand random layouts), and the C ABI's argument checks and no-device paths.  A sanitizer report aborts the driver.  (The Python
 CPU suite loads the product library through ctypes into an uninstrumented interpreter, so the sanitized build is
 exercised by this native driver instead.)"""
 import os
