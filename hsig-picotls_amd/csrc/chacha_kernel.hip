@@ -8,87 +8,16 @@
  * dealt to the lanes from the end of the data (poly1305.h describes the split); a lane encrypts its block, hashes the four
  * ciphertext blocks against r^4 .. r on top of acc r^(4G), and writes it.  The lanes' sums are joined by log2 G stages of one
  * multiplication and one DPP / permlane exchange each; lane 0 then runs the last partial ChaCha block, the length block
- * and the tag.  No LDS, no scratch: all state is in named registers (chacha20.h, poly1305.h).
+ * and the tag.  No LDS, no scratch: all state is in named registers (chacha20.h, poly1305.h).  What this kernel shares with
+ * chacha_runs_kernel.hip (the same arithmetic on data moved in contiguous runs, for host memory) is in chacha_kernel.h.
  *
  * Exact bytes: whole blocks are single 16-byte accesses inside the record; partial blocks go through load_block /
  * store_block of batch_kernel.h (whole dwords inside the record, then a 16-bit and / or an 8-bit access; byte by byte when
  * the layout is not 16-byte aligned).  Nothing outside a record's input (+ tag on open), AAD and output is touched.
  */
-#include "batch_kernel.h"
-#include "chacha20.h"
-#include "poly1305.h"
+#include "chacha_kernel.h"
 
 namespace ptls_hip {
-
-constexpr int CHACHA_WG = 256;
-
-template <int B>
-__device__ __forceinline__ uint32_t add_partner(uint32_t v)
-{
-    if constexpr (B == 0)
-        return v + dpp_mov<DPP_QUAD_XOR1>(v);
-    else if constexpr (B == 1)
-        return v + dpp_mov<DPP_QUAD_XOR2>(v);
-    else if constexpr (B == 2)
-        return v + dpp_mov<DPP_ROW_HALF_MIRROR>(v);
-    else if constexpr (B == 3)
-        return v + dpp_mov<DPP_ROW_MIRROR>(v);
-    else if constexpr (B == 4) {
-        const auto p = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-        return (uint32_t)p[0] + (uint32_t)p[1];
-    } else {
-        const auto p = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-        return (uint32_t)p[0] + (uint32_t)p[1];
-    }
-}
-
-/* stage B of the lane combination (poly1305.h): called with every lane of the wave active.  The partner of stages 2 and
- * 3 is the mirrored lane of the other half, which holds that half's common sum after the stages before. */
-template <int B, int LOG2G>
-__device__ __forceinline__ void combine(Poly &acc, Poly &sq, uint32_t lane)
-{
-    if constexpr (B < LOG2G) {
-        acc = poly_combine_stage(acc, sq, lane, B);
-        acc = Poly{add_partner<B>(acc.h0), add_partner<B>(acc.h1), add_partner<B>(acc.h2), add_partner<B>(acc.h3),
-                   add_partner<B>(acc.h4)};
-        sq = poly_mul(sq, sq);
-        combine<B + 1, LOG2G>(acc, sq, lane);
-    }
-}
-
-/* 16 input bytes of which the first `avail` (any int; <= 0 none, >= 16 all) are read from p, with the TLS 1.3 content type
- * put at byte `tpos` when that is 0 .. 15 */
-template <bool ALIGNED>
-__device__ __forceinline__ V4 load_in(const uint8_t *p, int avail, int tpos, uint32_t ttype)
-{
-    V4 v;
-    if (avail >= 16)
-        v = load_full(p);
-    else
-        v = load_block<ALIGNED>(p, avail < 0 ? 0 : avail);
-    if (tpos >= 0 && tpos < 16)
-        v = put_byte(v, tpos, ttype);
-    return v;
-}
-
-__device__ __forceinline__ ChaChaKey load_key(const ChaChaSlot *__restrict__ s)
-{
-    ChaChaKey k;
-    k.k0 = s->key[0], k.k1 = s->key[1], k.k2 = s->key[2], k.k3 = s->key[3];
-    k.k4 = s->key[4], k.k5 = s->key[5], k.k6 = s->key[6], k.k7 = s->key[7];
-    k.n0 = k.n1 = k.n2 = 0;
-    return k;
-}
-
-/* the header-protection mask of one sample: the first 16 keystream bytes of ChaCha20(hp key, counter = LE32(sample[0..4]),
- * nonce = sample[4..16]) (picotls's chacha20 cipher after do_init(sample), lib/cifra/chacha20.c:44-56) */
-__device__ __forceinline__ V4 chacha_mask(const ChaChaSlot *__restrict__ slot, V4 sample)
-{
-    ChaChaKey k = load_key(slot);
-    k.n0 = sample.w1, k.n1 = sample.w2, k.n2 = sample.w3;
-    const ChaChaBlock b = chacha20_block(k, sample.w0);
-    return V4{b.x0, b.x1, b.x2, b.x3};
-}
 
 template <int G, bool OPEN, bool ALIGNED>
 __global__ void __launch_bounds__(CHACHA_WG) chacha20poly1305_batch_kernel(const ChaChaArgs a)
@@ -137,15 +66,7 @@ __global__ void __launch_bounds__(CHACHA_WG) chacha20poly1305_batch_kernel(const
 
     Poly acc = poly_zero();
     if (valid && l == pad - 1) { /* the place before the first chunk: the AAD, zero-padded to whole blocks */
-        const uint32_t na = A >> 4;
-        for (uint32_t i = 0; i < na; ++i) {
-            const V4 v = load_full(aad_p + (size_t)i * 16);
-            acc = poly_step(acc, poly_block(v.w0, v.w1, v.w2, v.w3), r1);
-        }
-        if (A & 15u) {
-            const V4 v = load_block<ALIGNED>(aad_p + (size_t)na * 16, (int)(A & 15u));
-            acc = poly_step(acc, poly_block(v.w0, v.w1, v.w2, v.w3), r1);
-        }
+        acc = chacha_hash_aad<ALIGNED>(acc, aad_p, A, r1);
     }
 
     for (uint32_t t = 0; t < T; ++t) {
@@ -182,53 +103,11 @@ __global__ void __launch_bounds__(CHACHA_WG) chacha20poly1305_batch_kernel(const
         combine<0, LOG2G>(acc, sq, l);
     }
 
-    if (valid && l == 0) {
-        /* the last, partial ChaCha block */
-        const uint32_t ntail = L & 63u;
-        if (ntail != 0) {
-            const size_t off = (size_t)nfull * 64;
-            const ChaChaBlock ks = chacha20_block(k, nfull + 1);
-            const int avail = (int)(in_len - nfull * 64u); /* input bytes of the tail: ntail, or ntail - 1 with the type */
-            const int tpos = tflag ? (int)ntail - 1 : -1;
-#define PTLS_HIP_CHACHA_TAIL(J, K0, K1, K2, K3)                                                                                    \
-    if ((int)ntail > 16 * (J)) {                                                                                                   \
-        const int nb = (int)ntail - 16 * (J) < 16 ? (int)ntail - 16 * (J) : 16;                                                    \
-        const V4 iv = load_in<ALIGNED>(in_p + off + 16 * (J), avail - 16 * (J), tpos - 16 * (J), ttype);                            \
-        const V4 ov = mask_block(V4{iv.w0 ^ ks.K0, iv.w1 ^ ks.K1, iv.w2 ^ ks.K2, iv.w3 ^ ks.K3}, nb);                               \
-        const V4 cv = OPEN ? iv : ov;                                                                                              \
-        acc = poly_step(acc, poly_block(cv.w0, cv.w1, cv.w2, cv.w3), r1);                                                          \
-        store_block<ALIGNED>(out_p + off + 16 * (J), nb, ov);                                                                      \
-    }
-            PTLS_HIP_CHACHA_TAIL(0, x0, x1, x2, x3)
-            PTLS_HIP_CHACHA_TAIL(1, x4, x5, x6, x7)
-            PTLS_HIP_CHACHA_TAIL(2, x8, x9, x10, x11)
-            PTLS_HIP_CHACHA_TAIL(3, x12, x13, x14, x15)
-#undef PTLS_HIP_CHACHA_TAIL
-        }
-        /* LE64(aad_len) || LE64(len), then the tag */
-        acc = poly_step(acc, poly_block(A, 0, L, 0), r1);
-        uint32_t t0, t1, t2, t3;
-        poly_finish(acc, s0, s1, s2, s3, t0, t1, t2, t3);
-        if (OPEN) {
-            const V4 rt = load_full(in_p + L);
-            const bool ok = ((rt.w0 ^ t0) | (rt.w1 ^ t1) | (rt.w2 ^ t2) | (rt.w3 ^ t3)) == 0;
-            a.result[rec_i] = ok ? (uint64_t)L : ~(uint64_t)0;
-        } else {
-            store_full(out_p + L, V4{t0, t1, t2, t3});
-        }
-    }
+    if (valid && l == 0)
+        chacha_tail_tag<OPEN, ALIGNED>(a, rec_i, k, acc, r1, s0, s1, s2, s3, in_p, out_p, L, A, in_len, tflag, ttype);
 
-    if (!OPEN && a.supp != nullptr) {
-        /* header protection, after the record: the sample may cover the tag, and other lanes of this wave wrote most of
-         * it (the release / acquire pair completes their stores before the read, as in the AES batch kernel) */
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        if (valid && l == 0) {
-            const ptls_hip_supp_t sp = a.supp[rec_i];
-            if ((sp.flags & PTLS_HIP_SUPP_ENABLE) && sp.hp_key < a.hp_nslots)
-                store_full(a.mask + sp.mask_off, chacha_mask(a.hp_slots + sp.hp_key, load_full(a.out + sp.sample_off)));
-        }
-    }
+    if (!OPEN && a.supp != nullptr)
+        chacha_hp_step(a, rec_i, valid && l == 0);
 }
 
 /* standalone masks (the receive side): one thread per descriptor */

@@ -10,7 +10,8 @@
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places (no HIP call)
- *   pipeline.cpp       host-resident records: the mapped and copy transports over one slice launcher (launch_slice)
+ *   pipeline.cpp       host-resident records: the mapped and copy transports over one slice launcher (launch_slice), for
+ *                      AES-GCM or ChaCha20-Poly1305 keysets (the latter: chacha_kernel.hip, chacha_runs_kernel.hip)
  *   node.cpp           one batch over several devices, NUMA placement
  *   plugin_worker.cpp  the picotls plugin's runtime: the resident worker dispatch and pooled resources
  *   plugin.cpp         the picotls plugin objects (AEAD, CTR, ECB, fusion-style low-level API)

@@ -208,6 +208,8 @@ struct ChaChaArgs {
 
 /* lanes: 1, 4, 16 or 64 per record */
 int launch_chacha_batch(int lanes, bool open, void *stream, const ChaChaArgs &a, bool aligned);
+/* the same records through chacha_runs_kernel.hip (contiguous runs per instruction, for host memory); lanes: 4, 16 or 64 */
+int launch_chacha_runs(int lanes, bool open, void *stream, const ChaChaArgs &a, bool aligned);
 int launch_chacha_mask(const ptls_hip_supp_t *supp, uint32_t n, const uint8_t *src, uint8_t *mask, const ChaChaSlot *hp_slots,
                        uint32_t hp_nslots, unsigned grid, void *stream);
 int launch_chacha_keysetup(ChaChaSlot *slots, const uint8_t *keys, const uint8_t *ivs, uint32_t first, uint32_t count,

@@ -47,14 +47,19 @@ struct st_ptls_hip_pipeline_t {
     size_t slice_bytes, max_recs;
     int transport;      /* PTLS_HIP_TRANSPORT_*: what the caller asked for */
     int last_transport; /* what the last seal/open used */
+    int algo;           /* PTLS_HIP_ALGO_*: the keysets the pipeline serves */
+    int chacha_lanes;   /* ChaCha pipelines: 0 = from the slice's records, or the forced width (1, 4, 16, 64) */
+    int chacha_layout;  /* ... and PTLS_HIP_CHACHA_LAYOUT_* */
     PipeSlot slot[NSLOT];
     /* scratch of launch_slice: the slice's launch plan */
     std::vector<Chunk> ch;
     std::vector<uint32_t> order;
 };
 
-/* a slot's fixed buffers, for ptls_hip_pipeline_new and _free: f(&pointer, bytes, pinned host memory or device memory) */
-template <class F> static void slot_buffers(PipeSlot &s, size_t slice_bytes, size_t max_recs, F f)
+/* a slot's fixed buffers, for ptls_hip_pipeline_new and _free: f(&pointer, bytes, pinned host memory or device memory).
+ * The launch plan's buffers (chunks, record order) exist on AES-GCM pipelines only: the ChaCha kernels take the records in
+ * descriptor order. */
+template <class F> static void slot_buffers(PipeSlot &s, size_t slice_bytes, size_t max_recs, bool plan, F f)
 {
     f(&s.d_in, slice_bytes + 64, false);
     f(&s.d_out, slice_bytes + 64, false);
@@ -63,32 +68,41 @@ template <class F> static void slot_buffers(PipeSlot &s, size_t slice_bytes, siz
     f(&s.d_supp, max_recs * sizeof(ptls_hip_supp_t), false);
     f(&s.h_supp, max_recs * sizeof(ptls_hip_supp_t), true);
     f(&s.d_recs, max_recs * sizeof(ptls_hip_record_t), false);
-    f(&s.d_recs_ord, max_recs * sizeof(ptls_hip_record_t), false);
-    f(&s.h_recs_ord, max_recs * sizeof(ptls_hip_record_t), true);
-    f(&s.d_chunks, max_recs * sizeof(Chunk), false);
-    f(&s.d_order, max_recs * sizeof(uint32_t), false);
-    f(&s.h_order, max_recs * sizeof(uint32_t), true);
+    if (plan) {
+        f(&s.d_recs_ord, max_recs * sizeof(ptls_hip_record_t), false);
+        f(&s.h_recs_ord, max_recs * sizeof(ptls_hip_record_t), true);
+        f(&s.d_chunks, max_recs * sizeof(Chunk), false);
+        f(&s.d_order, max_recs * sizeof(uint32_t), false);
+        f(&s.h_order, max_recs * sizeof(uint32_t), true);
+    }
     f(&s.d_result, max_recs * sizeof(uint64_t), false);
     f(&s.h_recs, max_recs * sizeof(ptls_hip_record_t), true);
-    f(&s.h_chunks, max_recs * sizeof(Chunk), true);
+    if (plan)
+        f(&s.h_chunks, max_recs * sizeof(Chunk), true);
 }
 
 extern "C" ptls_hip_pipeline_t *ptls_hip_pipeline_new(ptls_hip_engine_t *eng, size_t slice_bytes)
 {
-    if (eng == nullptr || slice_bytes < (1u << 16)) {
+    return ptls_hip_pipeline_new_algo(eng, PTLS_HIP_ALGO_AESGCM, slice_bytes);
+}
+
+extern "C" ptls_hip_pipeline_t *ptls_hip_pipeline_new_algo(ptls_hip_engine_t *eng, int algo, size_t slice_bytes)
+{
+    if (eng == nullptr || slice_bytes < (1u << 16) || !(algo == PTLS_HIP_ALGO_AESGCM || algo == PTLS_HIP_ALGO_CHACHA20POLY1305)) {
         fail(PTLS_HIP_EINVAL, "pipeline_new: bad arguments");
         return nullptr;
     }
     DeviceGuard g(eng->device);
     auto *p = new st_ptls_hip_pipeline_t();
     p->eng = eng;
+    p->algo = algo;
     p->slice_bytes = slice_bytes;
     p->max_recs = slice_bytes / 16 + 1;
     bool ok = true;
     for (auto &s : p->slot) {
         ok = ok && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
              hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
-        slot_buffers(s, slice_bytes, p->max_recs, [&ok](auto **pp, size_t bytes, bool pinned) {
+        slot_buffers(s, slice_bytes, p->max_recs, algo == PTLS_HIP_ALGO_AESGCM, [&ok](auto **pp, size_t bytes, bool pinned) {
             ok = ok && (pinned ? hipHostMalloc(pp, bytes, hipHostMallocDefault) : hipMalloc(pp, bytes)) == hipSuccess;
         });
         s.busy = false;
@@ -109,7 +123,7 @@ extern "C" void ptls_hip_pipeline_free(ptls_hip_pipeline_t *p)
     for (auto &s : p->slot) {
         if (s.stream != nullptr)
             (void)hipStreamSynchronize(s.stream);
-        slot_buffers(s, p->slice_bytes, p->max_recs,
+        slot_buffers(s, p->slice_bytes, p->max_recs, p->algo == PTLS_HIP_ALGO_AESGCM,
                      [](auto **pp, size_t, bool pinned) { (void)(pinned ? hipHostFree(*pp) : hipFree(*pp)); });
         /* the copy transport's lazy staging (slot_gap_buffers, slot_mask_buffer) */
         (void)hipHostFree(s.h_gap);
@@ -137,6 +151,25 @@ extern "C" int ptls_hip_pipeline_set_transport(ptls_hip_pipeline_t *p, int trans
 extern "C" int ptls_hip_pipeline_last_transport(ptls_hip_pipeline_t *p)
 {
     return p->last_transport;
+}
+
+extern "C" int ptls_hip_pipeline_algo(ptls_hip_pipeline_t *p)
+{
+    return p != nullptr ? p->algo : fail(PTLS_HIP_EINVAL, "pipeline_algo: null pipeline");
+}
+
+extern "C" int ptls_hip_pipeline_set_chacha_lanes(ptls_hip_pipeline_t *p, int lanes, int layout)
+{
+    if (p == nullptr || p->algo != PTLS_HIP_ALGO_CHACHA20POLY1305)
+        return fail(PTLS_HIP_EINVAL, "pipeline_set_chacha_lanes: not a ChaCha20-Poly1305 pipeline");
+    if (!(lanes == 0 || lanes == 1 || lanes == 4 || lanes == 16 || lanes == 64) ||
+        !(layout == PTLS_HIP_CHACHA_LAYOUT_AUTO || layout == PTLS_HIP_CHACHA_LAYOUT_BLOCKS || layout == PTLS_HIP_CHACHA_LAYOUT_RUNS) ||
+        (layout == PTLS_HIP_CHACHA_LAYOUT_RUNS && lanes == 1))
+        return fail(PTLS_HIP_EINVAL, "pipeline_set_chacha_lanes: lanes must be 0, 1, 4, 16 or 64 and layout a "
+                                     "PTLS_HIP_CHACHA_LAYOUT_* (RUNS: 4 lanes or more)");
+    p->chacha_lanes = lanes;
+    p->chacha_layout = layout;
+    return 0;
 }
 
 extern "C" int ptls_hip_host_register(void *ptr, size_t len)
@@ -211,6 +244,50 @@ static int mapped_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu)
     return mean >= 64 ? SPARSE_LANES : mean >= 32 ? 32 : mean >= 16 ? std::max(lanes, 16) : lanes;
 }
 
+/* the record kernel of a ChaCha slice: lanes per record, and whether the runs kernel (chacha_runs_kernel.hip: one
+ * contiguous run of 16 x lanes bytes per group and instruction) or chacha_kernel.hip's (a lane per 64-byte block) */
+struct ChaChaPlan {
+    int lanes;
+    bool runs;
+};
+
+/* ... when the kernel reads and writes host memory.  As for AES the launch is PCIe-bound and the width decides, more than
+ * the layout does: a wide group of the block kernel touches the same contiguous span with its four instructions together.
+ * Measured (tools/bench_chacha_host.py, profiles/chacha_host_bench.log: 1 GiB in pinned memory, seal+open GiB/s, medians of
+ * three rounds of five steps, block kernel / runs kernel at 4, 16, 64 lanes; AES-128-GCM mapped in the same run beside it):
+ *   65 536 x 16 KiB, one key    36.3 / 34.4   38.0 / 38.1   39.9 / 41.3   AES 40.8
+ *   1 350 B over 65 536 keys    30.5 / 29.1   33.9 / 32.4   35.0 / 35.0   AES 35.0
+ *   256 B over 65 536 keys      21.9 / 20.5   22.4 / 22.6   20.1 / 19.6   AES 18.8
+ * (step-to-step spread mostly below 0.3, single steps up to 1.5 lower.)  The runs kernel wins only where every trip is full,
+ * 64 lanes on records of 64 blocks or more (+1.4, above the spread); at 1 350 B (21 blocks) the two tie at 64 lanes and the
+ * block kernel is ahead at 16 and 4; 64 lanes lose to 16 once a record has only four blocks.  So: records of 64 whole blocks
+ * or more in the mean take the runs kernel at 64 lanes, of 16 or more the block kernel at 64, shorter ones the block kernel
+ * at 16.  (Between 21 and 256 blocks, and below 4, nothing was measured: 64 is where a runs trip has no empty place.) */
+static ChaChaPlan mapped_chacha_lanes(const ptls_hip_record_t *recs, size_t n)
+{
+    double sum = 0;
+    for (size_t i = 0; i < n; ++i)
+        sum += (double)(recs[i].len / 64);
+    const double blocks = n != 0 ? sum / (double)n : 0;
+    return blocks >= 64 ? ChaChaPlan{64, true} : blocks >= 16 ? ChaChaPlan{64, false} : ChaChaPlan{16, false};
+}
+
+/* The copy transport's staging is device memory: the block kernel at the width of the device-resident calls.
+ * ptls_hip_pipeline_set_chacha_lanes overrides the width, the layout or both, on both transports; the runs kernel needs 4
+ * lanes, so a forced width of 1 keeps the block kernel and a forced RUNS widens an automatic 1 to 4. */
+static ChaChaPlan chacha_plan(const ptls_hip_pipeline_t *p, const ptls_hip_record_t *recs, size_t n, bool mapped)
+{
+    ChaChaPlan c = mapped ? mapped_chacha_lanes(recs, n) : ChaChaPlan{choose_chacha_lanes(recs, n, (unsigned)p->eng->ncu), false};
+    if (p->chacha_layout != PTLS_HIP_CHACHA_LAYOUT_AUTO)
+        c.runs = p->chacha_layout == PTLS_HIP_CHACHA_LAYOUT_RUNS;
+    if (p->chacha_lanes != 0)
+        c.lanes = p->chacha_lanes;
+    else if (c.runs && c.lanes < 4)
+        c.lanes = 4;
+    c.runs = c.runs && c.lanes >= 4;
+    return c;
+}
+
 /* wait for the slot's slice and deliver its masks (copy transport: the slice's masks arrived packed in s.h_mask) */
 static int slot_wait(PipeSlot &s)
 {
@@ -250,10 +327,19 @@ static void drain_slots(ptls_hip_pipeline_t *p)
  * the slot's staging.  `payload` queues what the transport itself uploads for the slice (copy: the records' bytes and
  * the gaps) between the descriptor uploads and the kernels, where the copy transport always queued it. */
 template <class Payload>
+static int launch_chacha_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, ChaChaPlan plan,
+                               const ModeInfo &m, const uint8_t *in, const uint8_t *aad, uint8_t *out, uint64_t *result,
+                               ptls_hip_keyset_t *hp_ks, bool have_supp, uint8_t *mask, Payload payload);
+
+/* (lanes: of the AES-GCM kernels; a ChaCha pipeline's slices take theirs from chacha_plan) */
+template <class Payload>
 static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, int lanes, const ModeInfo &m,
                         const uint8_t *in, const uint8_t *aad, uint8_t *out, uint64_t *result, ptls_hip_keyset_t *hp_ks,
-                        bool have_supp, uint8_t *mask, Payload payload)
+                        bool have_supp, uint8_t *mask, bool mapped, Payload payload)
 {
+    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305)
+        return launch_chacha_slice(p, s, ks, cnt, chacha_plan(p, s.h_recs, cnt, mapped), m, in, aad, out, result, hp_ks, have_supp,
+                                   mask, payload);
     const unsigned ncu = (unsigned)p->eng->ncu;
     const std::vector<Chunk> &ch = p->ch;
     bool aligned;
@@ -313,6 +399,53 @@ static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *
     return 0;
 }
 
+/* The same for a ChaCha20-Poly1305 keyset: no launch plan (the kernels take the records in descriptor order, as in
+ * run_batch: no chunks, no order, no chunk queue), so the descriptor uploads, the payload, and the three kernels. */
+template <class Payload>
+static int launch_chacha_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, ChaChaPlan plan,
+                               const ModeInfo &m, const uint8_t *in, const uint8_t *aad, uint8_t *out, uint64_t *result,
+                               ptls_hip_keyset_t *hp_ks, bool have_supp, uint8_t *mask, Payload payload)
+{
+    HIP_TRY(hipMemcpyAsync(s.d_recs, s.h_recs, cnt * sizeof(ptls_hip_record_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    if (have_supp)
+        HIP_TRY(hipMemcpyAsync(s.d_supp, s.h_supp, cnt * sizeof(ptls_hip_supp_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    if (int rc = payload())
+        return rc;
+    const unsigned egrid = record_grid(cnt, p->eng->ncu);
+    if (m.aad_in_out) {
+        const int eh = launch_tls13_headers(s.d_recs, (uint32_t)cnt, out, egrid, s.stream);
+        if (eh != 0)
+            return fail(PTLS_HIP_ELAUNCH, "pipeline: header kernel launch failed: %s", hipGetErrorString((hipError_t)eh));
+    }
+    ChaChaArgs a{};
+    a.recs = s.d_recs;
+    a.n = cnt;
+    a.in = in;
+    a.aad = m.aad_in_out ? out : m.aad_in_in ? in : aad;
+    a.out = out;
+    a.result = result;
+    a.slots = ks->d_chacha;
+    if (have_supp) {
+        a.supp = s.d_supp;
+        a.hp_slots = hp_ks->d_chacha;
+        a.hp_nslots = (uint32_t)hp_ks->nslots;
+        a.mask = mask;
+    }
+    bool aligned = ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.aad) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0;
+    for (size_t t = 0; t < cnt && aligned; ++t)
+        aligned = ((s.h_recs[t].in_off | s.h_recs[t].out_off | s.h_recs[t].aad_off) & 15) == 0;
+    const int e = plan.runs ? launch_chacha_runs(plan.lanes, m.open, s.stream, a, aligned)
+                            : launch_chacha_batch(plan.lanes, m.open, s.stream, a, aligned);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "pipeline: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (m.aad_in_in) {
+        const int ei = launch_tls13_inner(s.d_recs, (uint32_t)cnt, out, result, egrid, s.stream);
+        if (ei != 0)
+            return fail(PTLS_HIP_ELAUNCH, "pipeline: inner-plaintext kernel launch failed: %s", hipGetErrorString((hipError_t)ei));
+    }
+    return 0;
+}
+
 /* PTLS_HIP_TRANSPORT_MAPPED: the batch kernel reads the records from, and writes them to, the caller's pinned host
  * buffers over PCIe itself (their device addresses); no staging copies, no copy engines.  Only the descriptors,
  * the launch plan and the header-protection descriptors go through the slots' pinned staging.  Slices of at
@@ -341,8 +474,9 @@ static int pipeline_run_mapped(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, co
             std::memcpy(s.h_supp, supp + i, cnt * sizeof(ptls_hip_supp_t));
         /* results go straight to mapped memory, or through the slot when h_result is not mapped */
         uint64_t *res = d_res != nullptr ? d_res + i : s.d_result;
-        if (int rc = launch_slice(p, s, ks, cnt, mapped_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu), m, d_in, d_aad, d_out, res,
-                                  hp_ks, supp != nullptr, d_mask, [] { return 0; }))
+        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? mapped_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
+        if (int rc = launch_slice(p, s, ks, cnt, lanes, m, d_in, d_aad, d_out, res, hp_ks, supp != nullptr, d_mask, true,
+                                  [] { return 0; }))
             return rc;
         if (m.open && d_res == nullptr)
             HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream),
@@ -453,8 +587,9 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
             const int eg = launch_gap_scatter(s.d_gapd, (uint32_t)ngap, s.d_gap, s.d_out, s.stream);
             return eg == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline: gap-fill kernel launch failed: %s", hipGetErrorString((hipError_t)eg));
         };
-        if (int rc = launch_slice(p, s, ks, cnt, choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu), m, s.d_in, s.d_aad, s.d_out,
-                                  s.d_result, hp_ks, supp != nullptr, s.d_mask, payload))
+        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
+        if (int rc = launch_slice(p, s, ks, cnt, lanes, m, s.d_in, s.d_aad, s.d_out, s.d_result, hp_ks, supp != nullptr, s.d_mask,
+                                  false, payload))
             return rc;
         for (const Span &pc : pl.pieces)
             HIP_TRY(hipMemcpyAsync(hout + pc.lo, s.d_out + (pc.lo - pl.out_base), pc.hi - pc.lo, hipMemcpyDeviceToHost, s.stream),
@@ -477,9 +612,12 @@ static int pipeline_run(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, const ptl
                         const void *h_aad, void *h_out, uint64_t *h_result, PipeMode mode, ptls_hip_keyset_t *hp_ks = nullptr,
                         const ptls_hip_supp_t *supp = nullptr, void *h_mask = nullptr)
 {
-    /* the host transports plan their launches for the AES-GCM kernels only */
-    if ((ks != nullptr && ks->algo != PTLS_HIP_ALGO_AESGCM) || (hp_ks != nullptr && hp_ks->algo != PTLS_HIP_ALGO_AESGCM))
-        return fail(PTLS_HIP_EINVAL, "pipeline: ChaCha20-Poly1305 keysets are served by the device-resident batch calls only");
+    /* a pipeline serves the keysets of the algorithm it was made for (ptls_hip_pipeline_new: AES-GCM): its slots hold what
+     * that algorithm's launches need */
+    const int algo = p != nullptr ? p->algo : PTLS_HIP_ALGO_AESGCM;
+    if ((ks != nullptr && ks->algo != algo) || (hp_ks != nullptr && hp_ks->algo != algo))
+        return fail(PTLS_HIP_EINVAL, "pipeline: this pipeline serves %s keysets (ptls_hip_pipeline_new_algo)",
+                    algo == PTLS_HIP_ALGO_CHACHA20POLY1305 ? "ChaCha20-Poly1305" : "AES-GCM");
     if (supp != nullptr && (mode != PIPE_SEAL || hp_ks == nullptr || ks == nullptr || hp_ks->eng != ks->eng ||
                             hp_ks->key_size != ks->key_size || h_mask == nullptr))
         return fail(PTLS_HIP_EINVAL, "pipeline_seal_supp: the header-protection keyset must be on the same engine with the "

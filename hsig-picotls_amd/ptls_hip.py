@@ -29,6 +29,7 @@ TLS13_DECODE_ERROR = -50
 TLS13_SHORT_RECORD = -20  # a complete application-data record shorter than a tag (PTLS_ALERT_BAD_RECORD_MAC)
 TRANSPORT_AUTO, TRANSPORT_COPY, TRANSPORT_MAPPED = 0, 1, 2
 ALGO_AESGCM, ALGO_CHACHA20POLY1305 = 1, 2
+CHACHA_LAYOUT_AUTO, CHACHA_LAYOUT_BLOCKS, CHACHA_LAYOUT_RUNS = 0, 1, 2
 QUIC_PACKET_DTYPE = np.dtype([("pkt_off", "<u8"), ("data_off", "<u8"), ("pn", "<u8"), ("pkt_len", "<u4"), ("key", "<u4"),
                               ("hp_key", "<u4"), ("pn_offset", "<u2"), ("pn_len", "u1"), ("flags", "u1")])
 assert QUIC_PACKET_DTYPE.itemsize == 40
@@ -111,6 +112,9 @@ SIGNATURES = {
     "ptls_hip_pipeline_tls13_open": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "ptls_hip_pipeline_set_transport": (_i, [_vp, _i]),
     "ptls_hip_pipeline_last_transport": (_i, [_vp]),
+    "ptls_hip_pipeline_new_algo": (_vp, [_vp, _i, _sz]),
+    "ptls_hip_pipeline_algo": (_i, [_vp]),
+    "ptls_hip_pipeline_set_chacha_lanes": (_i, [_vp, _i, _i]),
     "ptls_hip_host_register": (_i, [_vp, _sz]),
     "ptls_hip_host_unregister": (_i, [_vp]),
     "ptls_hip_partition_bytes": (_i, [_vp, _sz, _sz, _vp]),
@@ -607,13 +611,26 @@ class AesEcb:
 class Pipeline:
     """host-resident seal/open: pinned H2D -> kernel -> D2H overlapped over three streams"""
 
-    def __init__(self, engine, slice_bytes=64 << 20, transport=None):
+    def __init__(self, engine, slice_bytes=64 << 20, transport=None, algo=None):
+        """algo: None (ptls_hip_pipeline_new: AES-GCM keysets), or ALGO_AESGCM / ALGO_CHACHA20POLY1305"""
         self.engine = engine
-        self.ptr = lib().ptls_hip_pipeline_new(engine.ptr, slice_bytes)
+        if algo is None:
+            self.ptr = lib().ptls_hip_pipeline_new(engine.ptr, slice_bytes)
+        else:
+            self.ptr = lib().ptls_hip_pipeline_new_algo(engine.ptr, algo, slice_bytes)
         if not self.ptr:
             raise HipError(f"ptls_hip_pipeline_new: {last_error()}")
         if transport is not None:
             self.set_transport(transport)
+
+    @property
+    def algo(self):
+        return lib().ptls_hip_pipeline_algo(self.ptr)
+
+    def set_chacha_lanes(self, lanes, layout=CHACHA_LAYOUT_AUTO):
+        """a ChaCha pipeline's record kernel: lanes per record (0 = automatic, 1, 4, 16, 64) and CHACHA_LAYOUT_AUTO / _BLOCKS /
+        _RUNS (tests and tuning)"""
+        _check(lib().ptls_hip_pipeline_set_chacha_lanes(self.ptr, lanes, layout), "pipeline_set_chacha_lanes")
 
     def set_transport(self, transport):
         """TRANSPORT_AUTO / TRANSPORT_COPY (copy engines + device staging) / TRANSPORT_MAPPED (kernels on the pinned host buffers)"""

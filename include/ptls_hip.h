@@ -144,7 +144,8 @@ size_t ptls_hip_keyset_size(ptls_hip_keyset_t *ks);
  * ChaCha20 header protection).  A ChaCha slot is the 32-byte key and the 12-byte static IV, 44 bytes of device memory:
  * nothing is expanded.  keyset_set / get_iv / set_iv / xor_iv / set_secrets / update_secrets (hash_size 32) / free work on
  * both kinds; seal / open calls take the kind their name says (2a below) and fail with PTLS_HIP_EINVAL, launching
- * nothing, on the other; the TLS 1.3 calls (2b) take either.  The host pipelines (2c) and nodes (2d) are AES-GCM only. */
+ * nothing, on the other; the TLS 1.3 calls (2b) take either.  A host pipeline (2c) serves the algorithm it was made for
+ * (ptls_hip_pipeline_new_algo); nodes (2d) are AES-GCM only. */
 #define PTLS_HIP_ALGO_AESGCM 1
 #define PTLS_HIP_ALGO_CHACHA20POLY1305 2
 ptls_hip_keyset_t *ptls_hip_keyset_new_algo(ptls_hip_engine_t *engine, int algo, size_t key_size, size_t nslots);
@@ -387,6 +388,25 @@ int ptls_hip_pipeline_tls13_open(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, 
 #define PTLS_HIP_TRANSPORT_MAPPED 2
 int ptls_hip_pipeline_set_transport(ptls_hip_pipeline_t *p, int transport);
 int ptls_hip_pipeline_last_transport(ptls_hip_pipeline_t *p);
+/* The algorithm a pipeline serves is fixed when it is made.  ptls_hip_pipeline_new makes AES-GCM pipelines, and so does
+ * ptls_hip_pipeline_new_algo with PTLS_HIP_ALGO_AESGCM (the same object); with PTLS_HIP_ALGO_CHACHA20POLY1305 it makes a
+ * pipeline for ChaCha20-Poly1305 keysets: the five calls above on both transports, with the argument rules, buffer checks and
+ * exact-bytes promises above; seal_supp takes a ChaCha header-protection keyset and writes the masks of
+ * ptls_hip_chacha20poly1305_seal_batch_supp.  Any other algo: NULL.  A call with a keyset (or header-protection keyset) of
+ * the other algorithm fails with PTLS_HIP_EINVAL and touches nothing. */
+ptls_hip_pipeline_t *ptls_hip_pipeline_new_algo(ptls_hip_engine_t *engine, int algo, size_t slice_bytes);
+int ptls_hip_pipeline_algo(ptls_hip_pipeline_t *p);
+/* For tests and tuning, on a ChaCha pipeline (PTLS_HIP_EINVAL on an AES-GCM one): the lanes per record of the slices' record
+ * kernel (0 = automatic, 1, 4, 16, 64) and how they move a record's whole 64-byte blocks.  BLOCKS: a lane loads and stores its
+ * own block, the kernel of the device-resident calls (2a).  RUNS (4 lanes or more): instruction j of a lane group moves the
+ * contiguous 16 x lanes bytes j of the group's 64 x lanes, and the lanes exchange the pieces inside quads; made for host
+ * memory, where the run length per instruction matters.  AUTO, as measured: on the mapped transport RUNS at
+ * 64 lanes for slices whose mean record has 64 whole blocks or more, BLOCKS at 64 or 16 lanes for shorter ones; BLOCKS on
+ * the copy transport's device staging.  Both layouts compute the same bytes. */
+#define PTLS_HIP_CHACHA_LAYOUT_AUTO 0
+#define PTLS_HIP_CHACHA_LAYOUT_BLOCKS 1
+#define PTLS_HIP_CHACHA_LAYOUT_RUNS 2
+int ptls_hip_pipeline_set_chacha_lanes(ptls_hip_pipeline_t *p, int lanes, int layout);
 int ptls_hip_host_register(void *ptr, size_t len);
 int ptls_hip_host_unregister(void *ptr);
 
