@@ -3,7 +3,9 @@
  * visibility, so the library exports only include/ptls_hip.h).
  *
  *   engine.cpp         errors, the AES T-table, engines (device memory pool, chunk queues), the start-up self-check
- *   keyset.cpp         keysets: AES key slots + GHASH basis, or ChaCha key slots; keys / IVs / TLS 1.3 secrets
+ *   keyset.cpp         keysets: AES key slots + GHASH basis, or ChaCha key slots; keys / IVs / TLS 1.3 secrets / QUIC
+ *                      secrets and Initial keys (kernels: keyschedule.hip, quic_keys.hip; the QUIC arithmetic shared with
+ *                      the CPU check: quic_keys.h)
  *   planner.cpp        the launch planner: lanes per record, chunks, grid
  *   batch.cpp          batches and the device-resident seal / open / header-protection calls
  *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls

@@ -235,6 +235,22 @@ int launch_quic_unprotect(int rounds, const QuicArgs &a, unsigned grid, void *st
 int launch_quic_protect(const ptls_hip_quic_packet_t *pkts, uint32_t n, uint8_t *pkt, const uint8_t *mask, unsigned grid,
                         void *stream);
 
+/* ---- QUIC key derivation (quic_keys.hip; the arithmetic shared with the CPU check: quic_keys.h) ---- */
+
+/* the HMAC-SHA256 pad states of the Initial salt (quic_keys.h HkPads<HkSha256>), hashed on the host once per call */
+struct QuicSaltPads {
+    uint32_t in[8], out[8];
+};
+
+/* per connection i < count: (update != 0: the "ku" step first, the new secret to secrets_out) key / iv / hp of secret i into
+ * keys + i * key_size, ivs + 12 i, hps + i * key_size (hps may be null); labels: PTLS_HIP_QUIC_LABELS_V1 / _V2 */
+int launch_quic_derive_keys(const uint8_t *secrets_in, uint8_t *secrets_out, uint32_t count, int hash_size, int key_size,
+                            int update, int labels, uint8_t *keys, uint8_t *ivs, uint8_t *hps, void *stream);
+/* per connection i < count and side s (0 client, 1 server): the AES-128 Initial keys of dcids + 20 i (dcid_lens[i] <= 20
+ * bytes) into entry 2 i + s of keys (16 bytes each), ivs (12) and hps (16) */
+int launch_quic_initial_keys(const QuicSaltPads &salt, const uint8_t *dcids, const uint8_t *dcid_lens, uint32_t count,
+                             int labels, uint8_t *keys, uint8_t *ivs, uint8_t *hps, void *stream);
+
 } // namespace ptls_hip
 
 #endif

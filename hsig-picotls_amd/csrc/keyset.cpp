@@ -11,6 +11,9 @@
 #include <cstring>
 
 #include "host.h"
+/* the Initial salt's HMAC pads are hashed on the host with the functions the kernels run (host-only qualifier) */
+#define GF128_FN static inline
+#include "quic_keys.h"
 
 /* ---------------------------------------------------------------------------------------------- */
 /* keysets                                                                                         */
@@ -201,6 +204,158 @@ extern "C" int ptls_hip_keyset_update_secrets(ptls_hip_keyset_t *ks, size_t firs
                                               void *stream)
 {
     return keyset_from_secrets(ks, first, count, secrets, hash_size, stream, true);
+}
+
+/* ---- QUIC: keys from traffic secrets or Destination Connection IDs (quic_keys.hip; include/ptls_hip.h 2f) ---- */
+
+/* what the three QUIC calls refuse about their keysets: `n` slots from `first` in ks and (unless null) hp_ks, which must be
+ * ks's twin (engine, algorithm, key size) */
+static int quic_keysets_check(const char *who, const ptls_hip_keyset_t *ks, const ptls_hip_keyset_t *hp_ks, size_t first, size_t n)
+{
+    if (hp_ks != nullptr && (hp_ks->eng != ks->eng || hp_ks->algo != ks->algo || hp_ks->key_size != ks->key_size))
+        return fail(PTLS_HIP_EINVAL, "%s: the keysets differ in engine, algorithm or key size", who);
+    if (first > ks->nslots || n > ks->nslots - first || (hp_ks != nullptr && (first > hp_ks->nslots || n > hp_ks->nslots - first)))
+        return fail(PTLS_HIP_EINVAL, "%s: slots %zu..%zu lie past a keyset", who, first, first + n);
+    return 0;
+}
+
+/* The device scratch of one QUIC call: the call's input (secrets, or connection IDs), then for n slots the packed raw keys,
+ * header-protection keys, IVs, and the zero IVs of the header-protection slots.  Key arrays first: they stay 16-byte aligned. */
+struct QuicScratch {
+    uint8_t *d = nullptr, *keys, *hps, *ivs, *zero_ivs;
+    size_t bytes, kbytes, ibytes;
+
+    hipError_t alloc(ptls_hip_keyset_t *ks, size_t in_bytes, size_t n)
+    {
+        in_bytes = (in_bytes + 15) & ~(size_t)15;
+        kbytes = n * ks->key_size, ibytes = n * 12;
+        bytes = in_bytes + 2 * kbytes + 2 * ibytes;
+        hipError_t e = dev_alloc(ks->eng, reinterpret_cast<void **>(&d), bytes);
+        keys = d + in_bytes, hps = keys + kbytes, ivs = hps + kbytes, zero_ivs = ivs + ibytes;
+        return e;
+    }
+};
+
+/* after the derivation launch: both key expansions, the IVs back to the host, the wait; then, whatever happened, the scrub
+ * of the scratch and its release.  Returns rc, or the first failure here. */
+static int quic_keys_finish(const char *who, int rc, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, QuicScratch &sc, size_t first,
+                            size_t n, void *back, const uint8_t *d_back, size_t back_bytes, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<uint8_t> h_ivs(sc.ibytes);
+    if (rc == 0) {
+        int e = 0;
+        if (hp_ks != nullptr && hipMemsetAsync(sc.zero_ivs, 0, sc.ibytes, s) != hipSuccess)
+            rc = fail(PTLS_HIP_ENODEV, "%s: memset failed", who);
+        else if ((e = keyset_setup(ks, sc.keys, sc.ivs, (uint32_t)first, (uint32_t)n, stream)) != 0 ||
+                 (hp_ks != nullptr && (e = keyset_setup(hp_ks, sc.hps, sc.zero_ivs, (uint32_t)first, (uint32_t)n, stream)) != 0))
+            rc = fail(PTLS_HIP_ELAUNCH, "%s: key setup launch failed: %s", who, hipGetErrorString((hipError_t)e));
+        else if (hipMemcpyAsync(h_ivs.data(), sc.ivs, sc.ibytes, hipMemcpyDeviceToHost, s) != hipSuccess ||
+                 (back != nullptr && hipMemcpyAsync(back, d_back, back_bytes, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+                 hipStreamSynchronize(s) != hipSuccess)
+            rc = fail(PTLS_HIP_ENODEV, "%s: derivation failed", who);
+    }
+    /* secrets and raw keys do not stay in device memory outside the expanded slots */
+    (void)hipMemsetAsync(sc.d, 0, sc.bytes, s);
+    (void)hipStreamSynchronize(s);
+    dev_free(ks->eng, sc.d); /* after the scrub: the stream was synchronized */
+    if (rc == 0) {
+        std::memcpy(&ks->ivs[first * 12], h_ivs.data(), sc.ibytes);
+        if (hp_ks != nullptr)
+            std::memset(&hp_ks->ivs[first * 12], 0, sc.ibytes);
+    }
+    std::fill(h_ivs.begin(), h_ivs.end(), 0);
+    return rc;
+}
+
+static int keyset_from_quic_secrets(const char *who, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t first, size_t count,
+                                    void *secrets, size_t hash_size, int labels, void *stream, bool update)
+{
+    if (ks == nullptr || (!update && hp_ks == nullptr) || secrets == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null keyset or secrets", who);
+    if (labels != PTLS_HIP_QUIC_LABELS_V1 && labels != PTLS_HIP_QUIC_LABELS_V2)
+        return fail(PTLS_HIP_EINVAL, "%s: labels must be PTLS_HIP_QUIC_LABELS_V1 or _V2 (got %d)", who, labels);
+    if (count > 0xffffffffu)
+        return fail(PTLS_HIP_EINVAL, "%s: count %zu is above 2^32 - 1", who, count);
+    /* SHA-384 goes with AES-256-GCM only (TLS_AES_256_GCM_SHA384); AES-128-GCM and ChaCha20-Poly1305 are SHA-256 suites */
+    const bool hash_ok = hash_size == 32 || (hash_size == 48 && ks->algo == PTLS_HIP_ALGO_AESGCM && ks->key_size == 32);
+    if (!hash_ok)
+        return fail(PTLS_HIP_EINVAL, "%s: hash_size %zu does not go with the keyset (algo %d, key_size %zu)", who, hash_size,
+                    ks->algo, ks->key_size);
+    if (int rc = quic_keysets_check(who, ks, hp_ks, first, count))
+        return rc;
+    if (count == 0)
+        return 0;
+    DeviceGuard g(ks->eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t sbytes = count * hash_size;
+    QuicScratch sc;
+    HIP_TRY(sc.alloc(ks, 2 * sbytes, count), PTLS_HIP_ENOMEM);
+    uint8_t *d_sec = sc.d, *d_next = sc.d + sbytes;
+    int rc = 0;
+    if (hipMemcpyAsync(d_sec, secrets, sbytes, hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = fail(PTLS_HIP_ENODEV, "%s: upload failed", who);
+    else if (int e = launch_quic_derive_keys(d_sec, update ? d_next : nullptr, (uint32_t)count, (int)hash_size, (int)ks->key_size,
+                                             update ? 1 : 0, labels, sc.keys, sc.ivs, hp_ks != nullptr ? sc.hps : nullptr, stream))
+        rc = fail(PTLS_HIP_ELAUNCH, "%s: derive launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    return quic_keys_finish(who, rc, ks, hp_ks, sc, first, count, update ? secrets : nullptr, d_next, sbytes, stream);
+}
+
+extern "C" int ptls_hip_keyset_set_quic_secrets(ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t first, size_t count,
+                                                const void *secrets, size_t hash_size, int labels, void *stream)
+{
+    return keyset_from_quic_secrets("keyset_set_quic_secrets", ks, hp_ks, first, count, const_cast<void *>(secrets), hash_size, labels,
+                                    stream, false);
+}
+
+extern "C" int ptls_hip_keyset_update_quic_secrets(ptls_hip_keyset_t *ks, size_t first, size_t count, void *secrets,
+                                                   size_t hash_size, int labels, void *stream)
+{
+    return keyset_from_quic_secrets("keyset_update_quic_secrets", ks, nullptr, first, count, secrets, hash_size, labels, stream, true);
+}
+
+extern "C" int ptls_hip_keyset_set_quic_initial(ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t first, size_t count,
+                                                const void *dcids, const uint8_t *dcid_lens, const void *salt, size_t salt_len,
+                                                int labels, void *stream)
+{
+    const char *who = "keyset_set_quic_initial";
+    if (ks == nullptr || hp_ks == nullptr || dcids == nullptr || dcid_lens == nullptr || salt == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null keyset, connection IDs or salt", who);
+    if (labels != PTLS_HIP_QUIC_LABELS_V1 && labels != PTLS_HIP_QUIC_LABELS_V2)
+        return fail(PTLS_HIP_EINVAL, "%s: labels must be PTLS_HIP_QUIC_LABELS_V1 or _V2 (got %d)", who, labels);
+    if (count > 0xffffffffu)
+        return fail(PTLS_HIP_EINVAL, "%s: count %zu is above 2^32 - 1", who, count);
+    if (salt_len < 1 || salt_len > HK_SALT_MAX)
+        return fail(PTLS_HIP_EINVAL, "%s: salt_len %zu is outside 1..64", who, salt_len);
+    if (ks->algo != PTLS_HIP_ALGO_AESGCM || ks->key_size != 16)
+        return fail(PTLS_HIP_EINVAL, "%s: Initial packets use AES-128-GCM: the keyset has algo %d, key_size %zu", who, ks->algo,
+                    ks->key_size);
+    if (int rc = quic_keysets_check(who, ks, hp_ks, first, 2 * count))
+        return rc;
+    for (size_t i = 0; i < count; ++i)
+        if (dcid_lens[i] > HK_DCID_STRIDE)
+            return fail(PTLS_HIP_EINVAL, "%s: dcid_lens[%zu] is %u, above 20", who, i, (unsigned)dcid_lens[i]);
+    if (count == 0)
+        return 0;
+    DeviceGuard g(ks->eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    /* the salt is the same HMAC key for every connection: its pads are hashed here, once per call */
+    HkPads<HkSha256> pads;
+    hk_salt_pads(pads, static_cast<const uint8_t *>(salt), salt_len);
+    QuicSaltPads sp;
+    std::memcpy(sp.in, pads.in, sizeof(sp.in));
+    std::memcpy(sp.out, pads.out, sizeof(sp.out));
+    const size_t dbytes = count * HK_DCID_STRIDE;
+    QuicScratch sc;
+    HIP_TRY(sc.alloc(ks, dbytes + count, 2 * count), PTLS_HIP_ENOMEM);
+    uint8_t *d_dcids = sc.d, *d_lens = sc.d + dbytes;
+    int rc = 0;
+    if (hipMemcpyAsync(d_dcids, dcids, dbytes, hipMemcpyHostToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(d_lens, dcid_lens, count, hipMemcpyHostToDevice, s) != hipSuccess)
+        rc = fail(PTLS_HIP_ENODEV, "%s: upload failed", who);
+    else if (int e = launch_quic_initial_keys(sp, d_dcids, d_lens, (uint32_t)count, labels, sc.keys, sc.ivs, sc.hps, stream))
+        rc = fail(PTLS_HIP_ELAUNCH, "%s: derive launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    return quic_keys_finish(who, rc, ks, hp_ks, sc, first, 2 * count, nullptr, nullptr, 0, stream);
 }
 
 extern "C" int ptls_hip_keyset_get_iv(ptls_hip_keyset_t *ks, size_t slot, void *iv)

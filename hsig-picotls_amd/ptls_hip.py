@@ -34,6 +34,9 @@ QUIC_PACKET_DTYPE = np.dtype([("pkt_off", "<u8"), ("data_off", "<u8"), ("pn", "<
                               ("hp_key", "<u4"), ("pn_offset", "<u2"), ("pn_len", "u1"), ("flags", "u1")])
 assert QUIC_PACKET_DTYPE.itemsize == 40
 QUIC_UNPROTECTED = 1
+QUIC_LABELS_V1, QUIC_LABELS_V2 = 1, 2  # "quic ..." (RFC 9001) / "quicv2 ..." (RFC 9369) key-derivation labels
+QUIC_DCID_STRIDE = 20  # bytes per connection ID passed to ptls_hip_keyset_set_quic_initial
+QUIC_V1_SALT = bytes.fromhex("38762cf7f55934b34d179ae6a4c80cadccbb7f0a")  # RFC 9001 §5.2; the library has no salt built in
 EINVAL = -1
 
 
@@ -89,6 +92,9 @@ SIGNATURES = {
     "ptls_hip_quic_batch_records": (_vp, [_vp]),
     "ptls_hip_quic_seal_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "ptls_hip_quic_open_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_keyset_set_quic_secrets": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _i, _vp]),
+    "ptls_hip_keyset_update_quic_secrets": (_i, [_vp, _sz, _sz, _vp, _sz, _i, _vp]),
+    "ptls_hip_keyset_set_quic_initial": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _i, _vp]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -261,6 +267,35 @@ class KeySet:
         _check(lib().ptls_hip_keyset_update_secrets(self.ptr, first, n, buf, hash_size, _stream(stream)),
                "keyset_update_secrets")
         return buf.raw
+
+    def set_quic_secrets(self, hp_ks, first, secrets, hash_size, labels=QUIC_LABELS_V1, stream=None):
+        """slots [first, first + n) of this keyset (key, IV) and of hp_ks (header-protection key) from n QUIC traffic secrets:
+        HKDF-Expand-Label "quic key" / "quic iv" / "quic hp" on the GPU (labels=QUIC_LABELS_V2: "quicv2 ...")"""
+        secrets = bytes(secrets)
+        n = len(secrets) // hash_size
+        assert len(secrets) == n * hash_size
+        _check(lib().ptls_hip_keyset_set_quic_secrets(self.ptr, hp_ks.ptr, first, n, secrets, hash_size, labels, _stream(stream)),
+               "keyset_set_quic_secrets")
+
+    def update_quic_secrets(self, first, secrets, hash_size, labels=QUIC_LABELS_V1, stream=None):
+        """QUIC key update of n connections ("quic ku"); re-keys this keyset and returns the next secrets"""
+        buf = ctypes.create_string_buffer(bytes(secrets), len(secrets))
+        n = len(secrets) // hash_size
+        assert len(secrets) == n * hash_size
+        _check(lib().ptls_hip_keyset_update_quic_secrets(self.ptr, first, n, buf, hash_size, labels, _stream(stream)),
+               "keyset_update_quic_secrets")
+        return buf.raw
+
+    def set_quic_initial(self, hp_ks, first, dcids, salt, labels=QUIC_LABELS_V1, stream=None):
+        """the Initial keys of len(dcids) connections (dcids: a list of bytes, 0..20 each) under the version's salt: client keys
+        in slot first + 2 i, server keys in slot first + 2 i + 1, of this keyset and of hp_ks (both AES-128)"""
+        dcids = [bytes(d) for d in dcids]
+        assert all(len(d) <= QUIC_DCID_STRIDE for d in dcids)
+        packed = b"".join(d.ljust(QUIC_DCID_STRIDE, b"\0") for d in dcids)
+        lens = bytes(len(d) for d in dcids)
+        salt = bytes(salt)
+        _check(lib().ptls_hip_keyset_set_quic_initial(self.ptr, hp_ks.ptr, first, len(dcids), packed, lens, salt, len(salt), labels,
+                                                      _stream(stream)), "keyset_set_quic_initial")
 
     def get_iv(self, slot):
         buf = ctypes.create_string_buffer(12)

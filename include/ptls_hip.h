@@ -519,6 +519,47 @@ int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks
                              uint64_t *result, uint64_t *pn_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------ *
+ * 2f. QUIC packet-protection keys, derived on the device (RFC 9001 §5.1, §5.2, §6; RFC 9369)     *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The keys of the 2e batches from traffic secrets or Destination Connection IDs, for many connections per call, as picotls
+ * derives them for one (ptls_hkdf_expand_label under the "tls13 quic " label prefix of ptls_aead_new, lib/picotls.c).  `ks`
+ * holds the AEAD keys and static IVs, `hp_ks` the header-protection keys (zero IVs); both must belong to one engine and be
+ * of one algorithm and key size.  `labels` selects the label prefix <p>: */
+#define PTLS_HIP_QUIC_LABELS_V1 1 /* "quic key", "quic iv", "quic hp", "quic ku"          (RFC 9001) */
+#define PTLS_HIP_QUIC_LABELS_V2 2 /* "quicv2 key", "quicv2 iv", "quicv2 hp", "quicv2 ku"  (RFC 9369) */
+
+/* set_quic_secrets: `secrets` = count traffic secrets of hash_size bytes in host memory (32: SHA-256; 48: SHA-384, for an
+ *   AES-256 keyset only; a ChaCha20-Poly1305 keyset takes 32 only).  Slot first + i of ks gets
+ *   key = HKDF-Expand-Label(secret_i, "<p> key", "", key_size) and iv = HKDF-Expand-Label(secret_i, "<p> iv", "", 12); slot
+ *   first + i of hp_ks gets HKDF-Expand-Label(secret_i, "<p> hp", "", key_size) with a zero IV.
+ * update_quic_secrets: the key update of RFC 9001 §6.  Every secret becomes HKDF-Expand-Label(secret, "<p> ku", "",
+ *   hash_size) -- written back to `secrets` -- and ks is re-keyed from the new secret.  The header-protection key does not
+ *   change with a key update, so there is no hp_ks.  A receiver keeps one keyset per key phase and updates the one of the
+ *   next phase.
+ * set_quic_initial: the Initial keys of RFC 9001 §5.2.  `dcids` = count client Destination Connection IDs at a 20-byte
+ *   stride in host memory, dcid_lens[i] = 0..20 the length of each; `salt` (1..64 bytes) is the version's initial salt,
+ *   supplied by the caller: 38762cf7f55934b34d179ae6a4c80cadccbb7f0a for QUIC v1 (RFC 9001 §5.2), with labels V1;
+ *   0dede3def700a6db819381be6e269dcbf9bd2ed9 for QUIC v2 (RFC 9369 §3.3.1), with labels V2.
+ *   initial_i = HKDF-Extract(salt, dcid_i); the client secret HKDF-Expand-Label(initial_i, "client in", "", 32) keys slot
+ *   first + 2 i and the server secret ("server in") slot first + 2 i + 1 of both keysets, by the rules of set_quic_secrets.
+ *   Initial packets are AES-128-GCM with SHA-256 whatever the connection negotiates later: both keysets must be AES-GCM
+ *   with key_size 16, and 2 * count slots are written from `first`.
+ * All three: synchronous like ptls_hip_keyset_set_secrets (`stream` is synchronised before the return); the host IV mirror
+ * (ptls_hip_keyset_get_iv) follows; secrets, initial secrets and raw keys are zeroed in device scratch memory before it is
+ * released; count == 0 returns 0.  PTLS_HIP_EINVAL with a message, nothing launched and no slot changed, for a null pointer,
+ * a range past either keyset, count > 2^32 - 1, a hash_size that does not go with the keyset, labels other than the two
+ * above, keysets of different engines, algorithms or key sizes, a dcid_lens[i] above 20, a salt_len outside 1..64, or a
+ * keyset other than AES-128-GCM in the Initial call. */
+int ptls_hip_keyset_set_quic_secrets(ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t first, size_t count,
+                                     const void *secrets, size_t hash_size, int labels, void *stream);
+int ptls_hip_keyset_update_quic_secrets(ptls_hip_keyset_t *ks, size_t first, size_t count, void *secrets, size_t hash_size,
+                                        int labels, void *stream);
+int ptls_hip_keyset_set_quic_initial(ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t first, size_t count,
+                                     const void *dcids, const uint8_t *dcid_lens, const void *salt, size_t salt_len, int labels,
+                                     void *stream);
+
+/* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
  *    seeded with seed ^ g(i), written at buf + recs[i].in_off for recs[i].len     *
  *    bytes, where g(i) = index[i] if `index` (device array of n uint64) is given, else base + i.     *
