@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "internal.h"
+#include "ctr_window.h"
 
 namespace ptls_hip {
 
@@ -185,31 +186,36 @@ __device__ __forceinline__ uint32_t lT2(const uint8_t *lds, uint32_t x, uint32_t
 /* Counter-mode shortcut (rounds 1-2).  For a record whose block counters stay below 2^16, the counter
  * word is 00 00 hi lo and everything else of the AES input is fixed per record, so after round 1 only
  * state columns 0 and 1 vary (they take counter bytes 15 and 14) and after round 2 every column is
- * (constant ^ two lookups).  CtrConst holds those per-record constants. */
-struct CtrConst {
-    uint32_t k10, k11; /* round-1 columns 0, 1 without their counter-byte term */
-    uint32_t k20, k21, k22, k23; /* round-2 columns without the terms from round-1 columns 0 and 1 */
-    uint32_t r03;      /* round key 0 word 3 (the counter word's whitening) */
+ * (constant ^ two lookups).  CtrConst holds those per-record constants; CtrWin those of one window of 256 counters
+ * (one value of counter byte 14), with which a block costs 1 + 4 lookups instead of 2 + 8.  The algebra is in
+ * ctr_window.h (it also compiles on the host, where tests/test_ctr_window_host.py checks it); LdsTab is its table
+ * accessor for this lane's copy of the LDS tables. */
+struct LdsTab {
+    const uint8_t *lds;
+    uint32_t lb;
+    template <int K>
+    __device__ __forceinline__ uint32_t t0(uint32_t x) const { return lT0<K>(lds, x, lb); }
+    template <int K>
+    __device__ __forceinline__ uint32_t t2(uint32_t x) const { return lT2<K>(lds, x, lb); }
 };
 
 __device__ __forceinline__ CtrConst ctr_const(const uint8_t *lds, uint32_t lb, const uint32_t *__restrict__ rk, uint32_t n0,
                                               uint32_t n1, uint32_t n2)
 {
-    const uint32_t s0 = n0 ^ rk[0], s1 = n1 ^ rk[1], s2 = n2 ^ rk[2], s3 = rk[3]; /* counter bytes 12,13 = 0 */
-    CtrConst c;
-    c.r03 = rk[3];
-    /* round 1: t_c = T0[s_c.b0] ^ T1[s_{c+1}.b1] ^ T2[s_{c+2}.b2] ^ T3[s_{c+3}.b3] ^ rk1_c */
-    c.k10 = lT0<0>(lds, s0, lb) ^ rotl8(lT0<1>(lds, s1, lb)) ^ lT2<2>(lds, s2, lb) ^ rk[4]; /* - T3[s3.b3] */
-    c.k11 = lT0<0>(lds, s1, lb) ^ rotl8(lT0<1>(lds, s2, lb)) ^ rotl8(lT2<3>(lds, s0, lb)) ^ rk[5]; /* - T2[s3.b2] */
-    const uint32_t t2 = lT0<0>(lds, s2, lb) ^ rotl8(lT0<1>(lds, s3, lb)) ^ lT2<2>(lds, s0, lb) ^ rotl8(lT2<3>(lds, s1, lb)) ^ rk[6];
-    const uint32_t t3 = lT0<0>(lds, s3, lb) ^ rotl8(lT0<1>(lds, s0, lb)) ^ lT2<2>(lds, s1, lb) ^ rotl8(lT2<3>(lds, s2, lb)) ^ rk[7];
-    /* round 2 constant parts (terms reading t2, t3) */
-    c.k20 = lT2<2>(lds, t2, lb) ^ rotl8(lT2<3>(lds, t3, lb)) ^ rk[8];
-    c.k21 = rotl8(lT0<1>(lds, t2, lb)) ^ lT2<2>(lds, t3, lb) ^ rk[9];
-    c.k22 = lT0<0>(lds, t2, lb) ^ rotl8(lT0<1>(lds, t3, lb)) ^ rk[10];
-    c.k23 = lT0<0>(lds, t3, lb) ^ rotl8(lT2<3>(lds, t2, lb)) ^ rk[11];
-    return c;
+    return ctr_const(LdsTab{lds, lb}, rk, n0, n1, n2);
 }
+
+/* which batch instantiations (lanes per record G) run the full-block stretch in the window form: the ones where the
+ * same-box A/B against the per-block form wins (EXPERIMENTS.md, "Window constants").  A lane's window lasts
+ * 256 / (PURE_BLOCKS G) iterations; from G = 8 on (16 iterations and fewer) the steps and the second descriptor load
+ * cost short records more than long ones gain. */
+__host__ __device__ constexpr bool ctr_window_form(int g)
+{
+    return g <= 4;
+}
+
+struct NoWin { /* ctr_ghash_skewed's window argument for the per-block form */
+};
 
 /* ---------------- the pieces of one round, issue and finish apart ----------------
  * The compiler, left alone, consumes each T-table lookup a few instructions after issuing it (lgkmcnt(0..4) waits), so a
@@ -273,17 +279,23 @@ __device__ __forceinline__ V4 last_finish(const RoundLoads &r, const uint32_t *_
  * s/KP+1 of block s%KP, then finishes the round that block (s-KP+1)%KP issued KP-1 segments earlier and
  * folds in the quarter multiply (its lookups go out first, so the fold does not wait for the AES ones).
  * GH = the multiply's table, issued in GH::PARTS parts of 4 lookups: GhMain (the batch kernel's 8-bit windows,
- * 4 parts) or GhNibble (the sparse kernel's per-wave 4-bit windows, 8 parts), defined with the GHASH helpers. */
-template <int ROUNDS, int KP, bool HASH, class GH>
+ * 4 parts) or GhNibble (the sparse kernel's per-wave 4-bit windows, 8 parts), defined with the GHASH helpers.
+ * WN = CtrWin[KP]: the window form, wn[b] = the constants of the window block slot b's counter lies in (the caller keeps
+ * them current); WN = NoWin: rounds 1-2 from CtrConst alone, 2 + 8 lookups per block. */
+template <int ROUNDS, int KP, bool HASH, class GH, class WN>
 __device__ __forceinline__ void ctr_ghash_skewed(const uint8_t *lds, uint32_t lb, const uint32_t *__restrict__ rk, const CtrConst &cc,
-                                                 const uint32_t (&cw)[KP], V4 (&ks)[KP], V4 &y, const V4 (&hx)[KP], const GH &gm)
+                                                 const uint32_t (&cw)[KP], V4 (&ks)[KP], V4 &y, const V4 (&hx)[KP], const GH &gm,
+                                                 const WN &wn)
 {
     constexpr int P = GH::PARTS; /* issue parts (4 lookups each) per GHASH multiply */
+    constexpr bool WIN = !std::is_same<WN, NoWin>::value;
     static_assert(P * KP <= KP * ROUNDS, "GHASH parts must fit in the segments");
+    const LdsTab tab{lds, lb};
     V4 s[KP];
     uint32_t t0[KP], t1[KP];
     RoundLoads R[KP];
     uint32_t M[KP][8];
+    uint32_t MW[KP][4]; /* the window form's lookups: round 1 [0], round 2 [0..3] */
     V4 G[4];
     V4 acc = V4{0, 0, 0, 0}, xr = V4{0, 0, 0, 0};
     constexpr int NSEG = KP * ROUNDS + KP - 1;
@@ -312,7 +324,14 @@ __device__ __forceinline__ void ctr_ghash_skewed(const uint8_t *lds, uint32_t lb
         __builtin_amdgcn_sched_barrier(0);
         if (seg < KP * ROUNDS) {
             const int b = seg % KP, r = seg / KP + 1;
-            if (r == 1) {
+            if (WIN && r <= 2) {
+                if constexpr (WIN) {
+                    if (r == 1)
+                        MW[b][0] = ctrw_r1_issue(tab, cc, cw[b]);
+                    else
+                        ctrw_r2_issue(tab, t0[b], MW[b]);
+                }
+            } else if (r == 1) {
                 const uint32_t x3 = cw[b] ^ cc.r03;
                 M[b][0] = lT2<3>(lds, x3, lb);
                 M[b][1] = lT2<2>(lds, x3, lb);
@@ -337,7 +356,17 @@ __device__ __forceinline__ void ctr_ghash_skewed(const uint8_t *lds, uint32_t lb
         if (seg >= KP - 1) {
             const int fs = seg - (KP - 1); /* the segment that issued the lookups finished here */
             const int b = fs % KP, r = fs / KP + 1;
-            if (r == 1) {
+            if (WIN && r <= 2) {
+                if constexpr (WIN) {
+                    if (r == 1) {
+                        t0[b] = ctrw_r1_finish(cc, MW[b][0]);
+                    } else {
+                        uint32_t c[4];
+                        ctrw_r2_finish(wn[b], MW[b], c);
+                        s[b] = V4{c[0], c[1], c[2], c[3]};
+                    }
+                }
+            } else if (r == 1) {
                 t0[b] = cc.k10 ^ rotl8(M[b][0]);
                 t1[b] = cc.k11 ^ M[b][1];
             } else if (r == 2) {
@@ -359,6 +388,14 @@ __device__ __forceinline__ void ctr_ghash_skewed(const uint8_t *lds, uint32_t lb
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+
+/* the per-block form (the generic elements, the sparse kernel) */
+template <int ROUNDS, int KP, bool HASH, class GH>
+__device__ __forceinline__ void ctr_ghash_skewed(const uint8_t *lds, uint32_t lb, const uint32_t *__restrict__ rk, const CtrConst &cc,
+                                                 const uint32_t (&cw)[KP], V4 (&ks)[KP], V4 &y, const V4 (&hx)[KP], const GH &gm)
+{
+    ctr_ghash_skewed<ROUNDS, KP, HASH>(lds, lb, rk, cc, cw, ks, y, hx, gm, NoWin{});
 }
 
 /* K independent blocks, round-interleaved */
@@ -516,6 +553,18 @@ __device__ __forceinline__ void ctr_ghash(const uint8_t *lds, uint32_t lb, const
                                           const uint32_t (&cw)[KP], V4 (&ks)[KP], V4 &y, const V4 (&hx)[KP], const GhLane &g)
 {
     ctr_ghash_skewed<ROUNDS, KP, HASH>(lds, lb, rk, cc, cw, ks, y, hx, GhMain{g});
+}
+
+/* the full-block stretch's call: WIN = the window form with the slots' window constants wn, else the per-block form */
+template <int ROUNDS, int KP, bool HASH, bool WIN>
+__device__ __forceinline__ void ctr_ghash_stretch(const uint8_t *lds, uint32_t lb, const uint32_t *__restrict__ rk, const CtrConst &cc,
+                                                  const CtrWin (&wn)[KP], const uint32_t (&cw)[KP], V4 (&ks)[KP], V4 &y,
+                                                  const V4 (&hx)[KP], const GhLane &g)
+{
+    if constexpr (WIN)
+        ctr_ghash_skewed<ROUNDS, KP, HASH>(lds, lb, rk, cc, cw, ks, y, hx, GhMain{g}, wn);
+    else
+        ctr_ghash_skewed<ROUNDS, KP, HASH>(lds, lb, rk, cc, cw, ks, y, hx, GhMain{g}, NoWin{});
 }
 
 /* y * P with a nibble table [p = 8w + j][v] (the G = 1 multiply by H, the sparse kernel's Horner steps).  One word
@@ -1263,25 +1312,33 @@ __global__ void __launch_bounds__(WGT)
             const bool valid = ridx < ch.count;
             /* descriptors in chunk order: the record is one load away (its caller index only matters for
              * result[] and supp[] at the end) */
-            const uint32_t pos = ch.first + (valid ? ridx : 0);
-            const ptls_hip_record_t rec = recs_ord[pos];
-            const uint32_t rec_i = order != nullptr ? order[pos] : pos; /* no order array: the plan keeps the caller's order */
-            const int L = valid ? (int)rec.len : 0;
-            const int A = valid ? (int)rec.aad_len : 0;
-            const int na = (A + 15) >> 4, nc = (L + 15) >> 4;
-            const int N = valid ? na + nc + 1 : 0;
-            const int i0 = (r + na) & (G - 1);
-            /* the lane's elements are i0 + m G for m < my_iters */
-            const int my_iters = N > i0 ? ((N - 1 - i0) >> LOG2G) + 1 : 0;
-
-            /* seal of a TLS 1.3 record: the last plaintext byte is the content type, not input */
-            const bool tflag = !OPEN && (rec.flags & 1u) != 0 && L > 0;
-            const uint32_t ttype = (rec.flags >> 8) & 0xffu;
-            const uint8_t *in_p = in + rec.in_off;
-            uint8_t *out_p = out + rec.out_off;
-            const uint8_t *aad_p = aad + rec.aad_off;
-            const uint32_t n0 = slot->iv[0], n1 = slot->iv[1] ^ bswap32((uint32_t)(rec.seq >> 32)),
-                           n2 = slot->iv[2] ^ bswap32((uint32_t)rec.seq);
+            /* The record and what follows from its descriptor alone, (re)loaded by load_rec: here and, in the window form,
+             * once more after the full-block stretch, whose loop has no register to spare at 768 threads for what only the
+             * elements after it need (one more descriptor load per task with a stretch). */
+            uint32_t rec_i, ttype, n0, n1, n2;
+            int L, A, na, nc, N, i0, my_iters;
+            bool tflag;
+            const uint8_t *in_p, *aad_p;
+            uint8_t *out_p;
+            auto load_rec = [&](uint32_t pos) __attribute__((always_inline)) {
+                const ptls_hip_record_t rec = recs_ord[pos];
+                rec_i = order != nullptr ? order[pos] : pos; /* no order array: the plan keeps the caller's order */
+                L = valid ? (int)rec.len : 0;
+                A = valid ? (int)rec.aad_len : 0;
+                na = (A + 15) >> 4, nc = (L + 15) >> 4;
+                N = valid ? na + nc + 1 : 0;
+                i0 = (r + na) & (G - 1);
+                /* the lane's elements are i0 + m G for m < my_iters */
+                my_iters = N > i0 ? ((N - 1 - i0) >> LOG2G) + 1 : 0;
+                /* seal of a TLS 1.3 record: the last plaintext byte is the content type, not input */
+                tflag = !OPEN && (rec.flags & 1u) != 0 && L > 0;
+                ttype = (rec.flags >> 8) & 0xffu;
+                in_p = in + rec.in_off;
+                out_p = out + rec.out_off;
+                aad_p = aad + rec.aad_off;
+                n0 = slot->iv[0], n1 = slot->iv[1] ^ bswap32((uint32_t)(rec.seq >> 32)), n2 = slot->iv[2] ^ bswap32((uint32_t)rec.seq);
+            };
+            load_rec(ch.first + (valid ? ridx : 0));
 
             V4 y = V4{0, 0, 0, 0}, ek0 = V4{0, 0, 0, 0};
             /* Iterations handle two Horner elements (i and i + G) of a lane; their AES blocks are independent
@@ -1400,6 +1457,9 @@ __global__ void __launch_bounds__(WGT)
                 uint8_t *dst = out_p + 16 * (size_t)(i0 - na + pm0 * G);
                 const uint32_t cbase = (uint32_t)(i0 - na + pm0 * G) + 2u;
                 V4 pend[KP], bufA[KP], bufB[KP];
+                /* the window form (ctr_window.h): per block slot, the constants of the window its counter is in */
+                constexpr bool WINF = ctr_window_form(G);
+                CtrWin wn[KP];
                 /* Deferred stores (seal of 16-byte aligned records whose output does not start on a 128-byte line).  An
                  * iteration writes KP G blocks of each record; with the record at block offset lo != 0 of a line, its last
                  * lo blocks fall into a line whose first 8 - lo blocks the NEXT iteration writes, a few microseconds later,
@@ -1442,6 +1502,26 @@ __global__ void __launch_bounds__(WGT)
                         store_full(dst + (spill[b] ? op : o) + 16 * b * G, spill[b] ? held : c);
                     }
                 };
+                /* A lane's counter of slot b advances by KP G per iteration.  win_refresh(itn) steps the window constants
+                 * to iteration itn's counters if any lane of the wave enters a new window there with either slot.  Every lane
+                 * steps its own, from the counters of iteration itn - 1 to those of itn, which changes nothing for a lane
+                 * that did not cross: the branch is wave-uniform and the iteration's body stays branch-free.  The step needs
+                 * k11 and r03 only, so the round-2 record constants are not held through the loop. */
+                auto win_refresh = [&](int itn) __attribute__((always_inline)) {
+                    if constexpr (WINF) {
+                        const LdsTab tab{lds, lb_aes};
+                        bool cross = false;
+#pragma unroll
+                        for (int b = 0; b < KP; ++b)
+                            cross |= ctr_window_crossed(cbase + (uint32_t)((itn * KP + b) * G), (uint32_t)(KP * G));
+                        if (__builtin_amdgcn_ballot_w64(cross) != 0) {
+#pragma unroll
+                            for (int b = 0; b < KP; ++b)
+                                wn[b] = ctr_window_step(tab, cc.k11, cc.r03, wn[b], bswap32(cbase + (uint32_t)(((itn - 1) * KP + b) * G)),
+                                                        bswap32(cbase + (uint32_t)((itn * KP + b) * G)));
+                        }
+                    }
+                };
                 auto stretch = [&](auto defer_tag) __attribute__((always_inline)) {
                     constexpr bool DEFER = decltype(defer_tag)::value;
                     /* one branch-free iteration; `hash_pending` (false: iteration 0) is a literal at every call site */
@@ -1456,9 +1536,11 @@ __global__ void __launch_bounds__(WGT)
                             k[b] = V4{n0, n1, n2, cw[b]};
                         }
                         __builtin_amdgcn_sched_barrier(0); /* keep the prefetch at the top of the iteration */
+                        if (it != 0)
+                            win_refresh(it);
                         if (OPEN) {
                             /* the input is the ciphertext: hash it in the same iteration */
-                            ctr_ghash<ROUNDS, KP, true>(lds, lb_aes, rk, cc, cw, k, y, d, gl);
+                            ctr_ghash_stretch<ROUNDS, KP, true, WINF>(lds, lb_aes, rk, cc, wn, cw, k, y, d, gl);
 #pragma unroll
                             for (int b = 0; b < KP; ++b) {
                                 store_full(dst + (size_t)(it * KP * G) * 16 + 16 * b * G, v4xor(d[b], k[b]));
@@ -1466,9 +1548,9 @@ __global__ void __launch_bounds__(WGT)
                         } else {
                             /* software pipelined: the ciphertext of iteration it is hashed during iteration it + 1 */
                             if (hash_pending)
-                                ctr_ghash<ROUNDS, KP, true>(lds, lb_aes, rk, cc, cw, k, y, pend, gl);
+                                ctr_ghash_stretch<ROUNDS, KP, true, WINF>(lds, lb_aes, rk, cc, wn, cw, k, y, pend, gl);
                             else
-                                ctr_ghash<ROUNDS, KP, false>(lds, lb_aes, rk, cc, cw, k, y, pend, gl);
+                                ctr_ghash_stretch<ROUNDS, KP, false, WINF>(lds, lb_aes, rk, cc, wn, cw, k, y, pend, gl);
 #pragma unroll
                             for (int b = 0; b < KP; ++b) {
                                 const V4 c = v4xor(d[b], k[b]);
@@ -1492,10 +1574,23 @@ __global__ void __launch_bounds__(WGT)
                                 store_full(dst + (size_t)((npure - 1) * KP * G) * 16 + 16 * b * G, pend[b]);
                     }
                 };
+                if constexpr (WINF) {
+#pragma unroll
+                    for (int b = 0; b < KP; ++b)
+                        wn[b] = ctr_window(LdsTab{lds, lb_aes}, cc, bswap32(cbase + (uint32_t)(b * G)));
+                }
                 if (DEFER_OK && wave_max(defer_any) != 0)
                     stretch(std::true_type{});
                 else
                     stretch(std::false_type{});
+                if constexpr (WINF) {
+                    /* the elements below need the record's descriptor and its round-2 constants again: loaded and
+                     * computed anew (the position made opaque), so that they are not held in registers through the loop */
+                    uint32_t pos = ch.first + (valid ? ridx : 0);
+                    asm volatile("" : "+v"(pos));
+                    load_rec(pos);
+                    cc = ctr_const(lds, lb_aes, rk, n0, n1, n2);
+                }
                 if (!OPEN) {
 #pragma unroll
                     for (int b = 0; b < KP; ++b)
