@@ -54,6 +54,10 @@ constexpr int PURE_BLOCKS = 2; /* data blocks per lane per iteration of the bran
                          1 = the task a wave drew past one chunk is dropped at the next chunk of the key run, 2 = cbase is not
                          advanced, 3 = the workgroup's task counter is not reset at a key switch (only at its first key) */
 #endif
+#ifndef OPEN_MUTANT
+#define OPEN_MUTANT 0 /* TEST-ONLY broken build (Makefile `mutants`, tests/test_gpu_open_matrix.py): 1 = open's tag compare
+                         ignores tag word 2 (bytes 8..11), so a record damaged only there is accepted */
+#endif
 #ifndef KS_STAMPS
 #define KS_STAMPS 0 /* DIAGNOSTIC builds only (tools/keyswitch_stamps.py): every wave sums the shader cycles it spends at key
                        switches (first barrier, table build, second barrier) and in total, and within its tasks (drawing
@@ -1628,7 +1632,8 @@ __global__ void __launch_bounds__(WGT)
                 const V4 tag = v4xor(s, ek0);
                 if (OPEN) {
                     const V4 rt = load_full(in_p + L);
-                    const bool ok = rt.w0 == tag.w0 && rt.w1 == tag.w1 && rt.w2 == tag.w2 && rt.w3 == tag.w3;
+                    const bool ok = rt.w0 == tag.w0 && rt.w1 == tag.w1 && (OPEN_MUTANT == 1 || rt.w2 == tag.w2) &&
+                                    rt.w3 == tag.w3;
                     result[rec_i] = ok ? (uint64_t)L : ~(uint64_t)0;
                 } else {
                     store_full(out_p + L, tag);

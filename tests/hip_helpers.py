@@ -5,8 +5,8 @@ import torch
 import ptls_hip
 
 
-def _dev(arr, total):
-    buf = np.zeros(max(total, 16) + 16, dtype=np.uint8)
+def _dev(arr, total, fill=0):
+    buf = np.full(max(total, 16) + 16, fill, dtype=np.uint8)
     if arr is not None:
         buf[: len(arr)] = arr
     return torch.from_numpy(buf).cuda()
@@ -49,8 +49,8 @@ class HostBatch:
         self.batch.close()
         self.keyset.close()
 
-    def _input(self, payloads):
-        buf = np.zeros(self.in_total, dtype=np.uint8)
+    def _input(self, payloads, fill=0):
+        buf = np.full(self.in_total, fill, dtype=np.uint8)
         for p, rec in zip(payloads, self.recs):
             if len(p):
                 buf[rec["in_off"]: rec["in_off"] + len(p)] = np.frombuffer(bytes(p), np.uint8)
@@ -77,17 +77,28 @@ class HostBatch:
         host = d_out.cpu().numpy()
         return [host[r["out_off"]: r["out_off"] + r["len"] + 16].tobytes() for r in self.recs]
 
-    def open(self, sealed, lanes=0, wg=0):
-        """sealed: list of ct||tag per record.  Returns (results, plaintexts)."""
-        self.batch.set_lanes(lanes)
-        self.batch.set_workgroup(wg)
-        d_in = _dev(self._input(sealed), self.in_total)
+    def open(self, sealed, lanes=0, wg=0, in_place=False, out_fill=0, res_fill=0):
+        """sealed: list of ct||tag per record.  Returns (results, plaintexts).
+        in_place: in == out, with the input layout for both (as seal).  out_fill / res_fill: the byte the output buffer
+        (in place: the input buffer's gaps) and the value `result` hold before the launch.  The whole output buffer
+        after the launch, slack included, is kept as self.out_image and the offsets of its records as self.out_offs."""
+        d_in = _dev(self._input(sealed, out_fill if in_place else 0), self.in_total, out_fill if in_place else 0)
         d_aad = _dev(self.aad, self.aad_total)
-        d_out = _dev(None, self.out_total)
-        d_res = torch.zeros(len(self.records), dtype=torch.int64, device="cuda")
-        self.batch.open(self.keyset, d_in, d_aad, d_out, d_res)
+        d_res = torch.full((len(self.records),), res_fill, dtype=torch.int64, device="cuda")
+        if in_place:
+            recs = self.recs.copy()
+            recs["out_off"] = recs["in_off"]
+            batch, d_out = ptls_hip.Batch(self.engine, recs), d_in
+        else:
+            recs, batch, d_out = self.recs, self.batch, _dev(None, self.out_total, out_fill)
+        batch.set_lanes(lanes)
+        batch.set_workgroup(wg)
+        batch.open(self.keyset, d_in, d_aad, d_out, d_res)
         torch.cuda.synchronize()
-        host = d_out.cpu().numpy()
+        if in_place:
+            batch.close()
+        host = self.out_image = d_out.cpu().numpy()
+        self.out_offs = [int(r["out_off"]) for r in recs]
         res = [int(x) & ((1 << 64) - 1) for x in d_res.cpu().numpy().tolist()]
-        pts = [host[r["out_off"]: r["out_off"] + r["len"]].tobytes() for r in self.recs]
+        pts = [host[r["out_off"]: r["out_off"] + r["len"]].tobytes() for r in recs]
         return res, pts

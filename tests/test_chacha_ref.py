@@ -95,3 +95,20 @@ def test_every_fixture_entry():
         out = chacha_ref.seal(key, iv, seq, aad, pt)
         assert hashlib.sha256(out).hexdigest() == e["sha256"] and sample_off == e["sample_off"]
         assert chacha_ref.hp_mask(hp_key, out[sample_off: sample_off + 16]).hex() == e["mask"], e["j"]
+
+
+def test_shared_open_equals_open():
+    """SharedOpen (one keystream per (key, nonce), shared between cases) against open_: growing and shrinking lengths under
+    one nonce, a damaged tag, ciphertext, AAD and sequence number"""
+    key, iv, aad = KEY_80_9F, bytes(range(1, 13)), bytes(range(21))
+    shared = chacha_ref.SharedOpen()
+    for L in (0, 1, 63, 64, 65, 200, 129, 17):
+        pt = hashlib.sha256(b"%d" % L).digest() * 7
+        out = chacha_ref.seal(key, iv, 5, aad, pt[:L])
+        cases = [(5, aad, out), (5, aad, out[:-1] + bytes([out[-1] ^ 0x80])), (5, aad[:-1], out), (4, aad, out)]
+        if L:
+            cases.append((5, aad, bytes([out[0] ^ 1]) + out[1:]))
+            cases.append((5, aad, out[:L - 1] + out[L:]))
+        for seq, a, sealed in cases:
+            assert shared.open_(key, iv, seq, a, sealed) == chacha_ref.open_(key, iv, seq, a, sealed), (L, seq)
+    assert shared.open_(key, iv, 5, aad, out) == (pt[:17], True)
