@@ -11,9 +11,11 @@
  *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
- *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places (no HIP call)
- *   pipeline.cpp       host-resident records: the mapped and copy transports over one slice launcher (launch_slice), for
- *                      AES-GCM or ChaCha20-Poly1305 keysets (the latter: chacha_kernel.hip, chacha_runs_kernel.hip)
+ *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
+ *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)
+ *   pipeline.cpp       host-resident records and QUIC packets: the mapped and copy transports over one slice launcher
+ *                      (launch_slice), for AES-GCM or ChaCha20-Poly1305 keysets (the latter: chacha_kernel.hip,
+ *                      chacha_runs_kernel.hip; the copy transport's QUIC header return: quic_slice_kernel.hip)
  *   node.cpp           one batch over several devices, NUMA placement
  *   plugin_worker.cpp  the picotls plugin's runtime: the resident worker dispatch and pooled resources
  *   plugin.cpp         the picotls plugin objects (AEAD, CTR, ECB, fusion-style low-level API)
@@ -181,6 +183,12 @@ inline void set_key_args(KernelArgs &a, const ptls_hip_engine_t *eng, const ptls
     a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
 }
 
+/* (pipeline.cpp, slice_plan.cpp) where slot_wait puts the unprotected header bytes of an opened packet: h_pkt + off and h_pkt + off + pn_offset */
+struct HdrDst {
+    uint64_t off;
+    uint32_t pn_offset;
+};
+
 class DeviceGuard {
   public:
     explicit DeviceGuard(int dev)
@@ -226,17 +234,21 @@ bool identity_order(const std::vector<uint32_t> &order, size_t n);
 /* what a pipeline slice runs: plain seal / open (AAD in its own buffer), or the TLS 1.3 record layer
  * (seal: the 5-byte headers are written into the output and read back as the AAD, like
  * ptls_hip_tls13_seal_batch; open: the AAD is the header in the received input, and the inner plaintext
- * is parsed after the open, like ptls_hip_tls13_open_batch) */
-enum PipeMode { PIPE_SEAL, PIPE_OPEN, PIPE_TLS13_SEAL, PIPE_TLS13_OPEN };
+ * is parsed after the open, like ptls_hip_tls13_open_batch), or QUIC packet protection (seal: the AAD is the header the
+ * caller wrote into the packet, in the output; open: the header in the received packet, in the input; no TLS framing,
+ * the header-protection kernels of quic_kernel.hip run around the record kernel instead) */
+enum PipeMode { PIPE_SEAL, PIPE_OPEN, PIPE_TLS13_SEAL, PIPE_TLS13_OPEN, PIPE_QUIC_SEAL, PIPE_QUIC_OPEN };
 
 /* what the mode means for the buffers: which side carries the tag, and the buffer the AAD lives in */
 struct ModeInfo {
     bool open;
-    bool aad_in_out, aad_in_in; /* the AAD is the header in the output (TLS 1.3 seal) / in the input (TLS 1.3 open) */
+    bool aad_in_out, aad_in_in; /* the AAD is the header in the output (TLS 1.3 / QUIC seal) / in the input (... open) */
     uint32_t tag_in, tag_out;   /* tag bytes after a record's input / output */
+    bool quic;                  /* QUIC packets: the header is the caller's (seal) or the packet's (open), not a TLS 1.3 one */
     ModeInfo(PipeMode m)
-        : open(m == PIPE_OPEN || m == PIPE_TLS13_OPEN), aad_in_out(m == PIPE_TLS13_SEAL), aad_in_in(m == PIPE_TLS13_OPEN),
-          tag_in(open ? 16 : 0), tag_out(open ? 0 : 16)
+        : open(m == PIPE_OPEN || m == PIPE_TLS13_OPEN || m == PIPE_QUIC_OPEN), aad_in_out(m == PIPE_TLS13_SEAL || m == PIPE_QUIC_SEAL),
+          aad_in_in(m == PIPE_TLS13_OPEN || m == PIPE_QUIC_OPEN), tag_in(open ? 16 : 0), tag_out(open ? 0 : 16),
+          quic(m == PIPE_QUIC_SEAL || m == PIPE_QUIC_OPEN)
     {
     }
 };
@@ -281,6 +293,29 @@ struct SlicePlan {
  * header-protection sample outside the slice's output */
 int plan_copy_slice(const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, size_t n, size_t i, const ModeInfo &m,
                     size_t slice_bytes, size_t max_recs, size_t hp_nslots, const CopyOrder &o, SlicePlan &pl);
+
+/* QUIC packets through the pipelines (ptls_hip_pipeline_quic_seal / _open).  quic_records: the record and header-protection
+ * descriptors of the packets as quic.cpp builds them per batch, in the caller's offsets (seal: supp[i] = sample at
+ * pn_offset + 4, mask at 16 i; open: from pn_len = 1, the packet-number length sits under header protection, so the record
+ * lengths are the plaintext AREAS pkt_len - pn_offset - 17, up to 3 bytes more than the kernel will write). */
+void quic_records(const ptls_hip_quic_packet_t *pkts, size_t n, bool open, std::vector<ptls_hip_record_t> &recs,
+                  std::vector<ptls_hip_supp_t> &supp);
+/* the per-packet refusals of ptls_hip_quic_batch_new; nullptr = none */
+const char *quic_packet_fault(const ptls_hip_quic_packet_t &p, bool open);
+
+/* a copy-transport slice of packets [i, s.j): plan_copy_slice over the packets' records (the cut also ends after
+ * slot_max_masks packets), then what only QUIC needs.  s.gaps / s.gap_src continue behind the gaps proper with, seal: every
+ * packet's header (pn_offset + pn_len bytes of h_pkt, which the record kernel reads as the AAD from the output staging);
+ * open: the last 3 bytes of every plaintext area (bytes of h_out the kernel may leave unwritten, which the copies back,
+ * planned for pn_len = 1, would otherwise fill with stale staging).  Gaps, headers and tails together fit the gap staging
+ * (slice_bytes) whenever the packets and the areas are disjoint; EINVAL where they are not and it overflows. */
+struct QuicSlicePlan {
+    SlicePlan s;
+    std::vector<ptls_hip_quic_packet_t> pkts; /* slice-local packet descriptors */
+    std::vector<HdrDst> hdr_dst;              /* open: where the packed header entry of slice packet t goes in h_pkt */
+};
+int plan_quic_slice(const ptls_hip_quic_packet_t *pkts, const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, size_t n,
+                    size_t i, const ModeInfo &m, size_t slice_bytes, size_t max_recs, const CopyOrder &o, QuicSlicePlan &pl);
 
 /* ---- batch.cpp ---- */
 /* one asynchronous seal / open launch of a planned batch (the device-resident calls and the TLS 1.3 ones), with the

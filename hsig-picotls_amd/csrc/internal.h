@@ -236,6 +236,11 @@ int launch_quic_unprotect(int rounds, const QuicArgs &a, unsigned grid, void *st
 int launch_quic_protect(const ptls_hip_quic_packet_t *pkts, uint32_t n, uint8_t *pkt, const uint8_t *mask, unsigned grid,
                         void *stream);
 
+/* quic_slice_kernel.hip, behind launch_quic_unprotect on a copy-transport slice: 8 bytes per packet at packed + 8 t = the
+ * count of unprotected header bytes (0 with PTLS_HIP_QUIC_UNPROTECTED, else 1 + pn_len), the first byte, the packet-number
+ * bytes, read from the packets at pkt */
+int launch_quic_pack_headers(const ptls_hip_quic_packet_t *pkts, uint32_t n, const uint8_t *pkt, void *packed, void *stream);
+
 /* ---- QUIC key derivation (quic_keys.hip; the arithmetic shared with the CPU check: quic_keys.h) ---- */
 
 /* the HMAC-SHA256 pad states of the Initial salt (quic_keys.h HkPads<HkSha256>), hashed on the host once per call */

@@ -39,6 +39,15 @@ struct PipeSlot {
     uint8_t *h_mask;
     uint8_t *mask_host;
     std::vector<uint64_t> mask_dst;
+    /* QUIC packets, allocated on the slot's first slice of them (slot_quic_buffers): the slice-local packet descriptors,
+     * pinned and on the device; open: the packet numbers when they cannot go straight to the caller's mapped array, and on
+     * the copy transport the packed header entries (quic_slice_kernel.hip), which arrive in h_hdr by one copy; entry t goes
+     * to hdr_host + hdr_dst[t] once the slice is done (slot_wait) */
+    ptls_hip_quic_packet_t *h_pkts, *d_pkts;
+    uint64_t *d_pn;
+    uint8_t *d_hdr, *h_hdr;
+    uint8_t *hdr_host;
+    std::vector<HdrDst> hdr_dst;
     bool busy;
 };
 
@@ -131,6 +140,11 @@ extern "C" void ptls_hip_pipeline_free(ptls_hip_pipeline_t *p)
         (void)hipHostFree(s.h_gapd);
         (void)hipFree(s.d_gapd);
         (void)hipHostFree(s.h_mask);
+        (void)hipHostFree(s.h_pkts);
+        (void)hipFree(s.d_pkts);
+        (void)hipFree(s.d_pn);
+        (void)hipFree(s.d_hdr);
+        (void)hipHostFree(s.h_hdr);
         if (s.done != nullptr)
             (void)hipEventDestroy(s.done);
         if (s.stream != nullptr)
@@ -288,7 +302,11 @@ static ChaChaPlan chacha_plan(const ptls_hip_pipeline_t *p, const ptls_hip_recor
     return c;
 }
 
-/* wait for the slot's slice and deliver its masks (copy transport: the slice's masks arrived packed in s.h_mask) */
+/* wait for the slot's slice and deliver its masks (copy transport: the slice's masks arrived packed in s.h_mask) and the
+ * unprotected header bytes of its QUIC packets (copy transport, open: packed in s.h_hdr, quic_slice_kernel.hip).
+ * Pinned buffers make slices overlap: while these header bytes are placed in h_pkt, a later slice's upload may be reading a
+ * span of h_pkt that contains them (descriptors not in h_pkt order).  That is harmless: the bytes belong to no packet of
+ * that slice, so nothing reads them from its staging, and nothing of its staging's span is copied back to h_pkt. */
 static int slot_wait(PipeSlot &s)
 {
     if (!s.busy)
@@ -297,6 +315,15 @@ static int slot_wait(PipeSlot &s)
     for (size_t t = 0; t < s.mask_dst.size(); ++t)
         std::memcpy(s.mask_host + s.mask_dst[t], s.h_mask + 16 * t, 16);
     s.mask_dst.clear();
+    for (size_t t = 0; t < s.hdr_dst.size(); ++t) {
+        const uint8_t *e = s.h_hdr + 8 * t;
+        if (e[0] == 0) /* PTLS_HIP_QUIC_UNPROTECTED: nothing is written */
+            continue;
+        uint8_t *hdr = s.hdr_host + s.hdr_dst[t].off;
+        hdr[0] = e[1];
+        std::memcpy(hdr + s.hdr_dst[t].pn_offset, e + 2, (size_t)e[0] - 1);
+    }
+    s.hdr_dst.clear();
     s.busy = false;
     return 0;
 }
@@ -318,6 +345,7 @@ static void drain_slots(ptls_hip_pipeline_t *p)
         (void)hipStreamSynchronize(s.stream);
         s.busy = false;
         s.mask_dst.clear(); /* the call failed: masks that were not delivered yet are not delivered */
+        s.hdr_dst.clear();  /* ... nor are header bytes */
     }
 }
 
@@ -361,7 +389,7 @@ static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *
     if (int rc = payload())
         return rc;
     const unsigned egrid = record_grid(cnt, p->eng->ncu);
-    if (m.aad_in_out) { /* TLS 1.3 seal: the headers, which the record kernel reads back as the AAD */
+    if (m.aad_in_out && !m.quic) { /* TLS 1.3 seal: the headers, which the record kernel reads back as the AAD */
         const int eh = launch_tls13_headers(s.d_recs, (uint32_t)cnt, out, egrid, s.stream);
         if (eh != 0)
             return fail(PTLS_HIP_ELAUNCH, "pipeline: header kernel launch failed: %s", hipGetErrorString((hipError_t)eh));
@@ -391,7 +419,7 @@ static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *
     const int e = launch_batch(lanes, ks->key_size == 16 ? 10 : 14, m.open, plan_wg(ch, lanes), grid, s.stream, a, aligned && base_aligned);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "pipeline: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (m.aad_in_in) { /* TLS 1.3 open: strip the inner plaintext's padding and content type */
+    if (m.aad_in_in && !m.quic) { /* TLS 1.3 open: strip the inner plaintext's padding and content type */
         const int ei = launch_tls13_inner(s.d_recs, (uint32_t)cnt, out, result, egrid, s.stream);
         if (ei != 0)
             return fail(PTLS_HIP_ELAUNCH, "pipeline: inner-plaintext kernel launch failed: %s", hipGetErrorString((hipError_t)ei));
@@ -412,7 +440,7 @@ static int launch_chacha_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_key
     if (int rc = payload())
         return rc;
     const unsigned egrid = record_grid(cnt, p->eng->ncu);
-    if (m.aad_in_out) {
+    if (m.aad_in_out && !m.quic) {
         const int eh = launch_tls13_headers(s.d_recs, (uint32_t)cnt, out, egrid, s.stream);
         if (eh != 0)
             return fail(PTLS_HIP_ELAUNCH, "pipeline: header kernel launch failed: %s", hipGetErrorString((hipError_t)eh));
@@ -438,7 +466,7 @@ static int launch_chacha_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_key
                             : launch_chacha_batch(plan.lanes, m.open, s.stream, a, aligned);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "pipeline: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (m.aad_in_in) {
+    if (m.aad_in_in && !m.quic) {
         const int ei = launch_tls13_inner(s.d_recs, (uint32_t)cnt, out, result, egrid, s.stream);
         if (ei != 0)
             return fail(PTLS_HIP_ELAUNCH, "pipeline: inner-plaintext kernel launch failed: %s", hipGetErrorString((hipError_t)ei));
@@ -525,6 +553,36 @@ static int slot_gap_buffers(ptls_hip_pipeline_t *p, PipeSlot &s)
     return 0;
 }
 
+/* a copy-transport slice's gaps (and what a QUIC slice stages with them, plan_quic_slice): the caller's bytes of h_out,
+ * gathered into the slot's pinned gap staging, uploaded and placed in d_out by gap_scatter_kernel, on s.stream before the
+ * slice's kernels */
+static int stage_gaps(ptls_hip_pipeline_t *p, PipeSlot &s, const SlicePlan &pl, const uint8_t *hout)
+{
+    const size_t ngap = pl.gaps.size();
+    if (ngap == 0)
+        return 0;
+    /* The gap staging is allocated here, behind the slot's first payload upload, where it always was, and not with
+     * the mask staging before the first enqueue.  Measured: allocated before the slot's first enqueue, every later
+     * slice's copies start only when the previous slice's copy back has ended, on any of the three streams (c2 copy
+     * seal+open 28.2 -> 24.0 GiB/s, same kernels and copies in the traces; profiles/pipeline_refactor_ab.log).
+     * Supposed cause: on a slot's first slice these milliseconds let its upload finish before the other slots make
+     * their first copies, and the runtime binds a stream to a copy engine at its first copy.  If the allocation
+     * fails, drain_slots waits for the uploads already queued. */
+    if (int rc = slot_gap_buffers(p, s))
+        return rc;
+    /* the caller's bytes of the gaps as they are now: no slice in flight writes them (plan_copy_slice fills no gap
+     * that another slice's record touches) */
+    for (size_t t = 0; t < ngap; ++t) {
+        s.h_gapd[t] = pl.gaps[t];
+        std::memcpy(s.h_gap + pl.gaps[t].src, hout + pl.gap_src[t].lo, pl.gaps[t].len);
+    }
+    const GapPiece &last = pl.gaps.back();
+    HIP_TRY(hipMemcpyAsync(s.d_gapd, s.h_gapd, ngap * sizeof(GapPiece), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    HIP_TRY(hipMemcpyAsync(s.d_gap, s.h_gap, (size_t)last.src + last.len, hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    const int eg = launch_gap_scatter(s.d_gapd, (uint32_t)ngap, s.d_gap, s.d_out, s.stream);
+    return eg == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline: gap-fill kernel launch failed: %s", hipGetErrorString((hipError_t)eg));
+}
+
 /* PTLS_HIP_TRANSPORT_COPY: slices staged through the slots' device buffers by the copy engines.  Per slice: its plan
  * first (plan_copy_slice, refusals included, while the slot's previous slice still runs), then the slot and its mask
  * staging, and only then the slice's first enqueue; after that nothing but a HIP call (an enqueue, or the first
@@ -556,7 +614,6 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
             std::memcpy(s.h_supp, pl.supp.data(), cnt * sizeof(ptls_hip_supp_t));
         s.mask_host = static_cast<uint8_t *>(h_mask);
         s.mask_dst.swap(pl.mask_dst);
-        const size_t ngap = pl.gaps.size();
         auto payload = [&]() -> int {
             HIP_TRY(hipMemcpyAsync(s.d_in + (pl.in.lo - pl.in_base), hin + pl.in.lo, pl.in.hi - pl.in.lo, hipMemcpyHostToDevice, s.stream),
                     PTLS_HIP_ENODEV);
@@ -564,28 +621,7 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
                 HIP_TRY(hipMemcpyAsync(s.d_aad + (pl.aad.lo - pl.aad_base), haad + pl.aad.lo, pl.aad.hi - pl.aad.lo,
                                        hipMemcpyHostToDevice, s.stream),
                         PTLS_HIP_ENODEV);
-            if (ngap == 0)
-                return 0;
-            /* The gap staging is allocated here, behind the slot's first payload upload, where it always was, and not with
-             * the mask staging before the first enqueue.  Measured: allocated before the slot's first enqueue, every later
-             * slice's copies start only when the previous slice's copy back has ended, on any of the three streams (c2 copy
-             * seal+open 28.2 -> 24.0 GiB/s, same kernels and copies in the traces; profiles/pipeline_refactor_ab.log).
-             * Supposed cause: on a slot's first slice these milliseconds let its upload finish before the other slots make
-             * their first copies, and the runtime binds a stream to a copy engine at its first copy.  If the allocation
-             * fails, drain_slots waits for the uploads already queued. */
-            if (int rc = slot_gap_buffers(p, s))
-                return rc;
-            /* the caller's bytes of the gaps as they are now: no slice in flight writes them (plan_copy_slice fills no gap
-             * that another slice's record touches) */
-            for (size_t t = 0; t < ngap; ++t) {
-                s.h_gapd[t] = pl.gaps[t];
-                std::memcpy(s.h_gap + pl.gaps[t].src, hout + pl.gap_src[t].lo, pl.gaps[t].len);
-            }
-            const GapPiece &last = pl.gaps.back();
-            HIP_TRY(hipMemcpyAsync(s.d_gapd, s.h_gapd, ngap * sizeof(GapPiece), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-            HIP_TRY(hipMemcpyAsync(s.d_gap, s.h_gap, (size_t)last.src + last.len, hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-            const int eg = launch_gap_scatter(s.d_gapd, (uint32_t)ngap, s.d_gap, s.d_out, s.stream);
-            return eg == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline: gap-fill kernel launch failed: %s", hipGetErrorString((hipError_t)eg));
+            return stage_gaps(p, s, pl, hout);
         };
         const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
         if (int rc = launch_slice(p, s, ks, cnt, lanes, m, s.d_in, s.d_aad, s.d_out, s.d_result, hp_ks, supp != nullptr, s.d_mask,
@@ -704,4 +740,283 @@ extern "C" int ptls_hip_pipeline_open(ptls_hip_pipeline_t *p, ptls_hip_keyset_t 
                                       const void *h_in, const void *h_aad, void *h_out, uint64_t *h_result)
 {
     return pipeline_run(p, ks, recs, n, h_in, h_aad, h_out, h_result, PIPE_OPEN);
+}
+
+/* ---------------------------------------------------------------------------------------------- */
+/* QUIC packets from and to host memory (include/ptls_hip.h 2g)                    */
+/* ---------------------------------------------------------------------------------------------- */
+
+/* the slot's staging for QUIC slices, allocated before the first enqueue of the slot's first such slice (as the mask
+ * staging is): at most slot_max_masks packets per slice on either transport */
+static int slot_quic_buffers(ptls_hip_pipeline_t *p, PipeSlot &s, bool open)
+{
+    const size_t cap = slot_max_masks(p->slice_bytes);
+    if (s.h_pkts == nullptr &&
+        (hipHostMalloc(&s.h_pkts, cap * sizeof(ptls_hip_quic_packet_t), hipHostMallocDefault) != hipSuccess ||
+         hipMalloc(&s.d_pkts, cap * sizeof(ptls_hip_quic_packet_t)) != hipSuccess)) {
+        (void)hipHostFree(s.h_pkts);
+        (void)hipFree(s.d_pkts);
+        s.h_pkts = s.d_pkts = nullptr;
+        return fail(PTLS_HIP_ENOMEM, "pipeline: cannot allocate the packet descriptor staging");
+    }
+    if (open && s.d_pn == nullptr &&
+        (hipMalloc(&s.d_pn, cap * sizeof(uint64_t)) != hipSuccess || hipMalloc(&s.d_hdr, cap * 8) != hipSuccess ||
+         hipHostMalloc(&s.h_hdr, cap * 8, hipHostMallocDefault) != hipSuccess)) {
+        (void)hipFree(s.d_pn);
+        (void)hipFree(s.d_hdr);
+        (void)hipHostFree(s.h_hdr);
+        s.d_pn = nullptr;
+        s.d_hdr = s.h_hdr = nullptr;
+        return fail(PTLS_HIP_ENOMEM, "pipeline: cannot allocate the packet-number and header staging");
+    }
+    return 0;
+}
+
+/* One slice of cnt packets on slot s, the same for both transports, once s.h_pkts, s.h_recs (and for seal s.h_supp: sample
+ * at pn_offset + 4, mask t at 16 t of s.d_mask) hold its slice-local descriptors.  On s.stream, through launch_slice:
+ *   seal: descriptors, `upload`, the record kernel with the header-protection masks (AAD = the header in pkt, where the
+ *         output goes), quic_protect_kernel;
+ *   open: descriptors, `upload`, quic_unprotect_kernel (it rewrites the slice's d_recs, and d_recs_ord through d_order when
+ *         the launch plan has an order: launch_slice uploaded the provisional ones before `upload`), on the copy transport
+ *         quic_pack_headers_kernel (`packed`), then the record open kernel (input and AAD in pkt).
+ * `upload` queues what the transport itself uploads.  in / pkt / out / result / pn_out are device addresses. */
+template <class Upload>
+static int launch_quic_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t cnt,
+                             int lanes, const ModeInfo &m, const uint8_t *in, uint8_t *pkt, uint8_t *out, uint64_t *result,
+                             uint64_t *pn_out, uint8_t *packed, bool mapped, Upload upload)
+{
+    HIP_TRY(hipMemcpyAsync(s.d_pkts, s.h_pkts, cnt * sizeof(ptls_hip_quic_packet_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    const bool chacha = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
+    /* one thread per packet; the AES unprotect kernel builds its T-tables per workgroup (the grid of quic.cpp) */
+    const size_t wgs = (cnt + 255) / 256;
+    auto between = [&]() -> int {
+        if (int rc = upload())
+            return rc;
+        if (!m.open)
+            return 0;
+        const bool ident = chacha || identity_order(p->order, cnt); /* (p->order: launch_slice's plan of this slice) */
+        QuicArgs a{};
+        a.pkts = s.d_pkts;
+        a.n = (uint32_t)cnt;
+        a.order = ident ? nullptr : s.d_order;
+        a.recs = s.d_recs;
+        a.recs_ord = ident ? nullptr : s.d_recs_ord;
+        a.pkt = pkt;
+        a.pn_out = pn_out;
+        a.hp_slots = hp_ks->d_slots;
+        a.hp_chacha = hp_ks->d_chacha;
+        a.t0 = p->eng->d_t0;
+        const unsigned grid = (unsigned)(chacha ? wgs : std::min<size_t>(wgs, (size_t)p->eng->ncu * 4));
+        int e = launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, a, grid, s.stream);
+        if (e == 0 && packed != nullptr)
+            e = launch_quic_pack_headers(s.d_pkts, (uint32_t)cnt, pkt, packed, s.stream);
+        return e == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline_quic_open: header kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    };
+    if (m.open)
+        return launch_slice(p, s, ks, cnt, lanes, m, pkt, nullptr, out, result, nullptr, false, nullptr, mapped, between);
+    if (int rc = launch_slice(p, s, ks, cnt, lanes, m, in, nullptr, pkt, nullptr, hp_ks, true, s.d_mask, mapped, between))
+        return rc;
+    const int e = launch_quic_protect(s.d_pkts, (uint32_t)cnt, pkt, s.d_mask, (unsigned)wgs, s.stream);
+    return e == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline_quic_seal: header kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+}
+
+/* the slice's descriptors into the slot's pinned staging: records and packets [i, i + cnt) in the offsets the kernels will
+ * use.  open: the provisional records are marked not 16-byte aligned (the real in_off is known only to
+ * quic_unprotect_kernel, and both build_chunks and launch_chacha_slice take `aligned` from these host descriptors);
+ * seal: mask t of the slice at 16 t of the slot's d_mask */
+static void fill_quic_slot(PipeSlot &s, const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp,
+                           const ptls_hip_quic_packet_t *pkts, size_t cnt, const ModeInfo &m)
+{
+    std::memcpy(s.h_recs, recs, cnt * sizeof(ptls_hip_record_t));
+    std::memcpy(s.h_pkts, pkts, cnt * sizeof(ptls_hip_quic_packet_t));
+    for (size_t t = 0; t < cnt; ++t) {
+        if (m.open) {
+            s.h_recs[t].in_off |= 1u;
+        } else {
+            s.h_supp[t] = supp[t];
+            s.h_supp[t].mask_off = 16 * (uint64_t)t;
+        }
+    }
+}
+
+/* MAPPED: the kernels run on the buffers' device addresses with the caller's offsets, the header kernels too (they read and
+ * rewrite the header bytes in host memory over PCIe); the masks stay in the slot's d_mask.  Slices of at most 4 x
+ * slice_bytes of payload and slot_max_masks packets.  Results and packet numbers go straight to mapped arrays, or through
+ * the slot when the caller's are not mapped. */
+static int quic_run_mapped(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const ptls_hip_quic_packet_t *pkts,
+                           const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, size_t n, const ModeInfo &m,
+                           const uint8_t *d_in, uint8_t *d_pkt, uint8_t *d_out, uint64_t *h_result, uint64_t *d_res,
+                           uint64_t *h_pn, uint64_t *d_pn)
+{
+    const size_t mslice = 4 * p->slice_bytes, cap = slot_max_masks(p->slice_bytes);
+    int k = 0;
+    for (size_t i = 0; i < n; ++k) {
+        size_t cnt = 0, bytes = 0;
+        while (i + cnt < n && cnt < cap && (cnt == 0 || bytes + recs[i + cnt].len <= mslice))
+            bytes += recs[i + cnt++].len;
+        PipeSlot &s = p->slot[k % NSLOT];
+        if (int rc = slot_wait(s))
+            return rc;
+        if (int rc = slot_quic_buffers(p, s, m.open))
+            return rc;
+        fill_quic_slot(s, recs + i, m.open ? nullptr : supp + i, pkts + i, cnt, m);
+        uint64_t *res = d_res != nullptr ? d_res + i : s.d_result, *pn = d_pn != nullptr ? d_pn + i : s.d_pn;
+        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? mapped_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
+        if (int rc = launch_quic_slice(p, s, ks, hp_ks, cnt, lanes, m, d_in, d_pkt, d_out, res, pn, nullptr, true, [] { return 0; }))
+            return rc;
+        if (m.open && d_res == nullptr)
+            HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
+        if (m.open && d_pn == nullptr)
+            HIP_TRY(hipMemcpyAsync(h_pn + i, s.d_pn, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
+        if (int rc = slot_submit(s))
+            return rc;
+        i += cnt;
+    }
+    for (auto &s : p->slot)
+        if (int rc = slot_wait(s))
+            return rc;
+    p->last_transport = PTLS_HIP_TRANSPORT_MAPPED;
+    return 0;
+}
+
+/* COPY: per slice its plan (plan_quic_slice), the slot and its staging, then on the slot's stream the input span (seal: the
+ * payloads; open: the packets), the gaps with the headers (seal) or the plaintext tails (open), the kernels, and the
+ * copies back: seal the packets' merged runs; open the plaintext areas' merged runs at their pn_len = 1 length, the packed
+ * header entries (slot_wait places them in h_pkt), the results and the packet numbers. */
+static int quic_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const ptls_hip_quic_packet_t *pkts,
+                         const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, size_t n, const ModeInfo &m, const uint8_t *h_in,
+                         uint8_t *h_pkt, uint8_t *h_out, uint64_t *h_result, uint64_t *h_pn)
+{
+    p->last_transport = PTLS_HIP_TRANSPORT_COPY;
+    const uint8_t *hin = m.open ? h_pkt : h_in; /* what the slice uploads a span of */
+    uint8_t *hout = m.open ? h_out : h_pkt;     /* where its output goes, and where its gaps come from */
+    CopyOrder ord;
+    plan_copy_order(recs, n, m, ord);
+    QuicSlicePlan pl;
+    int k = 0;
+    for (size_t i = 0; i < n; i = pl.s.j, ++k) {
+        if (int rc = plan_quic_slice(pkts, recs, supp, n, i, m, p->slice_bytes, p->max_recs, ord, pl))
+            return rc;
+        PipeSlot &s = p->slot[k % NSLOT];
+        if (int rc = slot_wait(s))
+            return rc;
+        if (int rc = slot_quic_buffers(p, s, m.open))
+            return rc;
+        const size_t cnt = pl.s.j - i;
+        fill_quic_slot(s, pl.s.recs.data(), pl.s.supp.data(), pl.pkts.data(), cnt, m);
+        s.hdr_host = h_pkt;
+        s.hdr_dst.swap(pl.hdr_dst);
+        auto upload = [&]() -> int {
+            if (pl.s.in.hi > pl.s.in.lo)
+                HIP_TRY(hipMemcpyAsync(s.d_in + (pl.s.in.lo - pl.s.in_base), hin + pl.s.in.lo, pl.s.in.hi - pl.s.in.lo,
+                                       hipMemcpyHostToDevice, s.stream),
+                        PTLS_HIP_ENODEV);
+            return stage_gaps(p, s, pl.s, hout);
+        };
+        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
+        if (int rc = launch_quic_slice(p, s, ks, hp_ks, cnt, lanes, m, s.d_in, m.open ? s.d_in : s.d_out, s.d_out, s.d_result, s.d_pn,
+                                       m.open ? s.d_hdr : nullptr, false, upload))
+            return rc;
+        for (const Span &pc : pl.s.pieces)
+            HIP_TRY(hipMemcpyAsync(hout + pc.lo, s.d_out + (pc.lo - pl.s.out_base), pc.hi - pc.lo, hipMemcpyDeviceToHost, s.stream),
+                    PTLS_HIP_ENODEV);
+        if (m.open) {
+            HIP_TRY(hipMemcpyAsync(s.h_hdr, s.d_hdr, 8 * cnt, hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
+            HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
+            HIP_TRY(hipMemcpyAsync(h_pn + i, s.d_pn, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
+        }
+        if (int rc = slot_submit(s))
+            return rc;
+    }
+    for (auto &s : p->slot)
+        if (int rc = slot_wait(s))
+            return rc;
+    return 0;
+}
+
+/* both calls: every refusal comes before anything is launched, copied or written */
+static int pipeline_quic_run(const char *who, ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                             const ptls_hip_quic_packet_t *pkts, size_t n, PipeMode mode, const void *h_in, void *h_pkt, void *h_out,
+                             uint64_t *h_result, uint64_t *h_pn)
+{
+    const ModeInfo m(mode);
+    if (p == nullptr || ks == nullptr || hp_ks == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null pipeline or keyset", who);
+    if (n != 0 && (pkts == nullptr || h_pkt == nullptr ||
+                   (m.open ? h_out == nullptr || h_result == nullptr || h_pn == nullptr : h_in == nullptr)))
+        return fail(PTLS_HIP_EINVAL, "%s: null buffer", who);
+    if (ks->eng != p->eng || hp_ks->eng != p->eng)
+        return fail(PTLS_HIP_EINVAL, "%s: pipeline and keysets must belong to the same engine", who);
+    if (hp_ks->algo != ks->algo || hp_ks->key_size != ks->key_size)
+        return fail(PTLS_HIP_EINVAL, "%s: the header-protection keyset must be of the AEAD keyset's algorithm and key size", who);
+    if (ks->algo != p->algo)
+        return fail(PTLS_HIP_EINVAL, "pipeline: this pipeline serves %s keysets (ptls_hip_pipeline_new_algo)",
+                    p->algo == PTLS_HIP_ALGO_CHACHA20POLY1305 ? "ChaCha20-Poly1305" : "AES-GCM");
+    if (n == 0)
+        return 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (const char *why = quic_packet_fault(pkts[i], m.open))
+            return fail(PTLS_HIP_EINVAL, "%s: packet %zu: %s", who, i, why);
+        if (pkts[i].key >= ks->nslots)
+            return fail(PTLS_HIP_EINVAL, "%s: packet %zu names key slot %u, the keyset has %zu", who, i, pkts[i].key, ks->nslots);
+        if (pkts[i].hp_key >= hp_ks->nslots)
+            return fail(PTLS_HIP_EINVAL, "%s: packet %zu names header-protection key slot %u, the keyset has %zu", who, i,
+                        pkts[i].hp_key, hp_ks->nslots);
+    }
+    std::vector<ptls_hip_record_t> recs;
+    std::vector<ptls_hip_supp_t> supp;
+    quic_records(pkts, n, m.open, recs, supp);
+    /* the bytes the kernels would touch in each buffer: [base + lo, base + need) */
+    uint64_t need_pkt = 0, need_data = 0, lo_pkt = UINT64_MAX, lo_data = UINT64_MAX;
+    for (size_t i = 0; i < n; ++i) {
+        need_pkt = std::max<uint64_t>(need_pkt, pkts[i].pkt_off + pkts[i].pkt_len);
+        lo_pkt = std::min<uint64_t>(lo_pkt, pkts[i].pkt_off);
+        need_data = std::max<uint64_t>(need_data, pkts[i].data_off + recs[i].len);
+        lo_data = std::min<uint64_t>(lo_data, pkts[i].data_off);
+    }
+    if (m.open) { /* host addresses, so the ranges compare exactly */
+        const uintptr_t pk = reinterpret_cast<uintptr_t>(h_pkt), ou = reinterpret_cast<uintptr_t>(h_out);
+        if (ou + lo_data < pk + need_pkt && pk + lo_pkt < ou + need_data)
+            return fail(PTLS_HIP_EINVAL, "%s: h_out overlaps the packets in h_pkt", who);
+    }
+    DeviceGuard g(p->eng->device);
+    void *h_data = m.open ? h_out : const_cast<void *>(h_in);
+    bool partial = false;
+    uint8_t *d_pkt = static_cast<uint8_t *>(mapped_span(h_pkt, need_pkt, &partial));
+    uint8_t *d_data = static_cast<uint8_t *>(mapped_span(h_data, need_data, &partial));
+    uint64_t *d_res = m.open ? static_cast<uint64_t *>(mapped_span(h_result, (uint64_t)n * 8, &partial)) : nullptr;
+    uint64_t *d_pn = m.open ? static_cast<uint64_t *>(mapped_span(h_pn, (uint64_t)n * 8, &partial)) : nullptr;
+    if (partial)
+        return fail(PTLS_HIP_EINVAL, "pipeline: a host buffer is pinned or registered only in part (its mapping ends before "
+                                     "the last byte the records touch): neither transport can use it");
+    int rc;
+    if (d_pkt != nullptr && d_data != nullptr && p->transport != PTLS_HIP_TRANSPORT_COPY) {
+        rc = quic_run_mapped(p, ks, hp_ks, pkts, recs.data(), supp.data(), n, m, m.open ? nullptr : d_data, d_pkt,
+                             m.open ? d_data : nullptr, h_result, d_res, h_pn, d_pn);
+    } else {
+        if (p->transport == PTLS_HIP_TRANSPORT_MAPPED)
+            return fail(PTLS_HIP_EINVAL, "%s: transport MAPPED needs the host buffers (packets and payloads) pinned or registered "
+                                         "over every byte the packets touch", who);
+        for (size_t i = 0; i < n; ++i)
+            if (pkts[i].pkt_len > p->slice_bytes)
+                return fail(PTLS_HIP_EINVAL, "%s: packet %zu does not fit a %zu-byte slice", who, i, p->slice_bytes);
+        rc = quic_run_copy(p, ks, hp_ks, pkts, recs.data(), supp.data(), n, m, static_cast<const uint8_t *>(h_in),
+                           static_cast<uint8_t *>(h_pkt), static_cast<uint8_t *>(h_out), h_result, h_pn);
+    }
+    if (rc != 0)
+        drain_slots(p);
+    return rc;
+}
+
+extern "C" int ptls_hip_pipeline_quic_seal(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                           const ptls_hip_quic_packet_t *pkts, size_t n, const void *h_in, void *h_pkt)
+{
+    return pipeline_quic_run("pipeline_quic_seal", p, ks, hp_ks, pkts, n, PIPE_QUIC_SEAL, h_in, h_pkt, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ptls_hip_pipeline_quic_open(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                           const ptls_hip_quic_packet_t *pkts, size_t n, void *h_pkt, void *h_out,
+                                           uint64_t *h_result, uint64_t *h_pn_out)
+{
+    return pipeline_quic_run("pipeline_quic_open", p, ks, hp_ks, pkts, n, PIPE_QUIC_OPEN, nullptr, h_pkt, h_out, h_result, h_pn_out);
 }

@@ -39,16 +39,7 @@ extern "C" ptls_hip_quic_batch_t *ptls_hip_quic_batch_new(ptls_hip_engine_t *eng
     }
     /* every quantity of these checks is host-known; nothing touches the device before they pass */
     for (size_t i = 0; i < n; ++i) {
-        const ptls_hip_quic_packet_t &p = pkts[i];
-        const char *why = nullptr;
-        if (p.pn_offset == 0)
-            why = "pn_offset is 0";
-        else if (p.pkt_len < (uint32_t)p.pn_offset + 4u + 16u)
-            why = "the header-protection sample at pn_offset + 4 would leave the packet (pkt_len < pn_offset + 20)";
-        else if (!open && (p.pn_len < 1 || p.pn_len > 4))
-            why = "pn_len must be 1..4";
-        else if (!open && p.pn >= ((uint64_t)1 << 62))
-            why = "the packet number must be below 2^62";
+        const char *why = quic_packet_fault(pkts[i], open != 0);
         if (why != nullptr) {
             fail(PTLS_HIP_EINVAL, "quic_batch_new: packet %zu: %s", i, why);
             return nullptr;
@@ -58,33 +49,20 @@ extern "C" ptls_hip_quic_batch_t *ptls_hip_quic_batch_new(ptls_hip_engine_t *eng
     q->eng = eng;
     q->n = n;
     q->open = open != 0;
-    std::vector<ptls_hip_record_t> recs(n);
-    std::vector<ptls_hip_supp_t> supp(q->open ? 0 : n);
+    std::vector<ptls_hip_record_t> recs;
+    std::vector<ptls_hip_supp_t> supp; /* seal: sample of packet i -> mask at 16 i */
+    quic_records(pkts, n, q->open, recs, supp);
     for (size_t i = 0; i < n; ++i) {
         const ptls_hip_quic_packet_t &p = pkts[i];
         if (i == 0 || p.key > q->max_key)
             q->max_key = p.key, q->max_key_at = i;
         if (i == 0 || p.hp_key > q->max_hp_key)
             q->max_hp_key = p.hp_key, q->max_hp_key_at = i;
-        /* open: the packet-number length sits under header protection.  The plan is made from pn_len = 1 (lengths are a
-         * performance hint to the planner: the kernels take every length from the descriptor they read at launch), and
-         * as not 16-byte aligned: quic_unprotect_kernel writes the real in_off */
-        const uint32_t pn_len = q->open ? 1u : p.pn_len;
-        ptls_hip_record_t &r = recs[i];
-        r.aad_off = p.pkt_off;
-        r.aad_len = (uint32_t)p.pn_offset + pn_len;
-        r.len = p.pkt_len - r.aad_len - 16u;
-        r.seq = p.pn;
-        r.key = p.key;
-        r.flags = 0;
-        if (q->open) {
-            r.in_off = (p.pkt_off + r.aad_len) | 1u;
-            r.out_off = p.data_off;
-        } else {
-            r.in_off = p.data_off;
-            r.out_off = p.pkt_off + r.aad_len;
-            supp[i] = ptls_hip_supp_t{p.pkt_off + p.pn_offset + 4u, 16 * (uint64_t)i, p.hp_key, PTLS_HIP_SUPP_ENABLE};
-        }
+        /* open: the packet-number length sits under header protection.  The plan is made from pn_len = 1 (quic_records;
+         * lengths are a performance hint to the planner: the kernels take every length from the descriptor they read at
+         * launch), and as not 16-byte aligned: quic_unprotect_kernel writes the real in_off */
+        if (q->open)
+            recs[i].in_off |= 1u;
     }
     q->inner = ptls_hip_batch_new(eng, recs.data(), n, stream);
     if (q->inner == nullptr) { /* (the message is batch_new's) */

@@ -178,3 +178,81 @@ int plan_copy_slice(const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, 
     }
     return 0;
 }
+
+/* ---------------------------------------------------------------------------------------------- */
+/* QUIC packets (ptls_hip_pipeline_quic_seal / _open)                                               */
+/* ---------------------------------------------------------------------------------------------- */
+
+const char *quic_packet_fault(const ptls_hip_quic_packet_t &p, bool open)
+{
+    if (p.pn_offset == 0)
+        return "pn_offset is 0";
+    if (p.pkt_len < (uint32_t)p.pn_offset + 4u + 16u)
+        return "the header-protection sample at pn_offset + 4 would leave the packet (pkt_len < pn_offset + 20)";
+    if (!open && (p.pn_len < 1 || p.pn_len > 4))
+        return "pn_len must be 1..4";
+    if (!open && p.pn >= ((uint64_t)1 << 62))
+        return "the packet number must be below 2^62";
+    return nullptr;
+}
+
+void quic_records(const ptls_hip_quic_packet_t *pkts, size_t n, bool open, std::vector<ptls_hip_record_t> &recs,
+                  std::vector<ptls_hip_supp_t> &supp)
+{
+    recs.resize(n);
+    supp.resize(open ? 0 : n);
+    for (size_t i = 0; i < n; ++i) {
+        const ptls_hip_quic_packet_t &p = pkts[i];
+        const uint32_t pn_len = open ? 1u : p.pn_len;
+        ptls_hip_record_t &r = recs[i];
+        r.aad_off = p.pkt_off;
+        r.aad_len = (uint32_t)p.pn_offset + pn_len;
+        r.len = p.pkt_len - r.aad_len - 16u;
+        r.seq = p.pn;
+        r.key = p.key;
+        r.flags = 0;
+        if (open) {
+            r.in_off = p.pkt_off + r.aad_len;
+            r.out_off = p.data_off;
+        } else {
+            r.in_off = p.data_off;
+            r.out_off = p.pkt_off + r.aad_len;
+            supp[i] = ptls_hip_supp_t{p.pkt_off + p.pn_offset + 4u, 16 * (uint64_t)i, p.hp_key, PTLS_HIP_SUPP_ENABLE};
+        }
+    }
+}
+
+int plan_quic_slice(const ptls_hip_quic_packet_t *pkts, const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp, size_t n,
+                    size_t i, const ModeInfo &m, size_t slice_bytes, size_t max_recs, const CopyOrder &o, QuicSlicePlan &pl)
+{
+    /* at most slot_max_masks packets: their masks (seal) or packed headers (open) share the slot's small staging.  Every
+     * hp_key was checked against its keyset before the first slice, so the kernel writes every mask. */
+    const size_t cap = std::min(max_recs, slot_max_masks(slice_bytes) + 1);
+    SlicePlan &s = pl.s;
+    if (int rc = plan_copy_slice(recs, supp, n, i, m, slice_bytes, cap, SIZE_MAX, o, s))
+        return rc;
+    s.mask_dst.clear(); /* the masks stay in the slot's d_mask for quic_protect_kernel */
+    const size_t cnt = s.j - i;
+    const uint64_t pkt_base = m.open ? s.in_base : s.out_base, data_base = m.open ? s.out_base : s.in_base;
+    pl.pkts.assign(pkts + i, pkts + s.j);
+    pl.hdr_dst.clear();
+    uint64_t staged = s.gaps.empty() ? 0 : (uint64_t)s.gaps.back().src + s.gaps.back().len;
+    for (size_t t = 0; t < cnt; ++t) {
+        ptls_hip_quic_packet_t &p = pl.pkts[t];
+        const ptls_hip_record_t &r = recs[i + t];
+        /* seal: the header the caller wrote; open: the last 3 bytes of the area (r.len >= 3: pkt_len >= pn_offset + 20) */
+        const uint64_t lo = m.open ? p.data_off + r.len - 3 : p.pkt_off;
+        const uint32_t len = m.open ? 3u : r.aad_len;
+        if (staged + len > slice_bytes)
+            return fail(PTLS_HIP_EINVAL, "pipeline_quic_%s: the %s of the slice at packet %zu overlap", m.open ? "open" : "seal",
+                        m.open ? "plaintext areas" : "packets", i);
+        s.gaps.push_back(GapPiece{lo - s.out_base, (uint32_t)staged, len});
+        s.gap_src.push_back(Span{lo, lo + len});
+        staged += len;
+        if (m.open)
+            pl.hdr_dst.push_back(HdrDst{p.pkt_off, p.pn_offset});
+        p.pkt_off -= pkt_base;
+        p.data_off -= data_base;
+    }
+    return 0;
+}

@@ -116,6 +116,8 @@ SIGNATURES = {
     "ptls_hip_pipeline_tls13_seal": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
     "ptls_hip_pipeline_seal_supp": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "ptls_hip_pipeline_tls13_open": (_i, [_vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "ptls_hip_pipeline_quic_seal": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "ptls_hip_pipeline_quic_open": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp]),
     "ptls_hip_pipeline_set_transport": (_i, [_vp, _i]),
     "ptls_hip_pipeline_last_transport": (_i, [_vp]),
     "ptls_hip_pipeline_new_algo": (_vp, [_vp, _i, _sz]),
@@ -704,6 +706,20 @@ class Pipeline:
         recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
         _check(lib().ptls_hip_pipeline_tls13_open(self.ptr, keyset.ptr, recs.ctypes.data, len(recs), _ptr(h_wire), _ptr(h_out),
                                                   _ptr(h_result)), "pipeline_tls13_open")
+
+    def quic_seal(self, keyset, hp_keyset, pkts, h_in, h_pkt):
+        """pkts = host numpy array (QUIC_PACKET_DTYPE): payloads at h_in + data_off -> protected packets at h_pkt + pkt_off (the
+        unprotected headers are already there); h_in may be h_pkt (in place)"""
+        pkts = np.ascontiguousarray(pkts, dtype=QUIC_PACKET_DTYPE)
+        _check(lib().ptls_hip_pipeline_quic_seal(self.ptr, keyset.ptr, hp_keyset.ptr, pkts.ctypes.data, len(pkts), _ptr(h_in),
+                                                 _ptr(h_pkt)), "pipeline_quic_seal")
+
+    def quic_open(self, keyset, hp_keyset, pkts, h_pkt, h_out, h_result, h_pn_out):
+        """unprotects the headers in h_pkt, decodes the packet numbers into h_pn_out, opens the payloads into h_out + data_off;
+        h_result[i] = payload length or UINT64_MAX"""
+        pkts = np.ascontiguousarray(pkts, dtype=QUIC_PACKET_DTYPE)
+        _check(lib().ptls_hip_pipeline_quic_open(self.ptr, keyset.ptr, hp_keyset.ptr, pkts.ctypes.data, len(pkts), _ptr(h_pkt),
+                                                 _ptr(h_out), _ptr(h_result), _ptr(h_pn_out)), "pipeline_quic_open")
 
     def close(self):
         if self.ptr:

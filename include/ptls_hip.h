@@ -354,7 +354,8 @@ int ptls_hip_tls13_open_batch(ptls_hip_batch_t *batch, ptls_hip_keyset_t *ks, co
  * slice's record.  The masks of seal_supp are written packed into the slice's staging, come back by one
  * copy per slice and are placed at their mask_off by the host: no other byte of h_mask is read or written,
  * the masks of a slice may lie anywhere in h_mask (between other slices' masks too), and a slice ends
- * after slice_bytes / 64 masks. */
+ * after slice_bytes / 64 masks.  Whole QUIC packets, header protection included, go through the same pipelines with
+ * ptls_hip_pipeline_quic_seal / _open (2g). */
 typedef struct st_ptls_hip_pipeline_t ptls_hip_pipeline_t;
 ptls_hip_pipeline_t *ptls_hip_pipeline_new(ptls_hip_engine_t *engine, size_t slice_bytes);
 void ptls_hip_pipeline_free(ptls_hip_pipeline_t *p);
@@ -510,7 +511,8 @@ ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *batch);
  * known only once the header is unprotected), and the seal call's masks pass through a buffer of the batch.  Calls on one
  * QUIC batch must therefore be ordered: on the same stream, or by the caller's own synchronisation.
  *
- * Out of scope: the host pipelines (2c) and the node API (2d); splitting coalesced datagrams and parsing long-header fields
+ * Packets in host memory go through the host pipelines with ptls_hip_pipeline_quic_seal / _open (2g).
+ * Out of scope: the node API (2d); splitting coalesced datagrams and parsing long-header fields
  * (the caller supplies pn_offset); Retry and Version Negotiation packets (they carry no packet protection); choosing the
  * key by key phase on the device (the AES planner needs every packet's key slot on the host). */
 int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
@@ -545,6 +547,7 @@ int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks
  *   first + 2 i and the server secret ("server in") slot first + 2 i + 1 of both keysets, by the rules of set_quic_secrets.
  *   Initial packets are AES-128-GCM with SHA-256 whatever the connection negotiates later: both keysets must be AES-GCM
  *   with key_size 16, and 2 * count slots are written from `first`.
+ * The keysets serve the device-resident batches of 2e and, for packets in host memory, the pipeline calls of 2g alike.
  * All three: synchronous like ptls_hip_keyset_set_secrets (`stream` is synchronised before the return); the host IV mirror
  * (ptls_hip_keyset_get_iv) follows; secrets, initial secrets and raw keys are zeroed in device scratch memory before it is
  * released; count == 0 returns 0.  PTLS_HIP_EINVAL with a message, nothing launched and no slot changed, for a null pointer,
@@ -558,6 +561,46 @@ int ptls_hip_keyset_update_quic_secrets(ptls_hip_keyset_t *ks, size_t first, siz
 int ptls_hip_keyset_set_quic_initial(ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t first, size_t count,
                                      const void *dcids, const uint8_t *dcid_lens, const void *salt, size_t salt_len, int labels,
                                      void *stream);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2g. QUIC packet protection from and to host memory (the pipelines of 2c over the packets of 2e) *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The two calls of 2e for packets that lie in host memory (recvmmsg / sendmmsg buffers), through a pipeline of 2c: the same
+ * slots, slicing, overlap and transports.  `pkts` is a HOST array of n descriptors; the descriptor, the header rules, the
+ * packet-number decode, PTLS_HIP_QUIC_UNPROTECTED, h_result and h_pn_out are exactly those of ptls_hip_quic_seal_batch /
+ * _open_batch, with offsets relative to the host buffers.  Synchronous like every pipeline call: on return every byte is in
+ * host memory.  The pipeline may be of either algorithm (ptls_hip_pipeline_new_algo); ks and hp_ks are of that algorithm and
+ * of one key size (AES-128-GCM, AES-256-GCM, ChaCha20-Poly1305), filled by ptls_hip_keyset_set or derived on the device (2f):
+ * a receiver whose header-protection keys exist only in a device keyset opens its host-resident packets with this call.
+ *
+ * Transports as in 2c.  AUTO: MAPPED when h_pkt and h_in (seal) or h_pkt and h_out (open) are pinned or registered over
+ * every byte the packets touch, COPY otherwise.  h_result and h_pn_out may be unmapped on MAPPED; they then travel through
+ * the slot.  A slice holds at most slice_bytes / 64 packets on either transport.
+ *
+ * Exact bytes, on both transports, for pageable and pinned buffers:
+ *   seal: in h_pkt exactly the pkt_len bytes of each packet change; h_in is not written; h_in == h_pkt with
+ *         data_off = pkt_off + pn_offset + pn_len (in place, the way QUIC stacks build packets) is allowed.
+ *   open: in h_pkt only the first byte and the pn_len packet-number bytes of each packet are written, and nothing for a
+ *         packet with PTLS_HIP_QUIC_UNPROTECTED.  In h_out exactly the pkt_len - pn_offset - pn_len - 16 plaintext bytes at
+ *         data_off are written, on failure too, where pn_len is what the unprotected first byte says.  h_result[i] and
+ *         h_pn_out[i] are written for every i < n and nothing past them.
+ * The caller cannot know pn_len before the call.  The plaintext AREAS [data_off, data_off + pkt_len - pn_offset - 17) (the
+ * pn_len = 1 size) must therefore be pairwise disjoint and must not overlap any packet in h_pkt.  (The copy transport brings
+ * each area back whole: up to 3 bytes at its end that the kernel does not write come back as the caller had them, read when
+ * the slice is planned, like the gaps of 2c.  Do not modify them, or the headers of a seal call, during the call.)
+ *
+ * PTLS_HIP_EINVAL with a message (which names the packet where one is at fault), nothing launched or copied and no caller
+ * byte touched: the per-packet refusals of ptls_hip_quic_batch_new; a key or hp_key outside its keyset; keysets of
+ * different engines, algorithms or key sizes, or not of the pipeline's algorithm; a null pipeline or keyset, or with
+ * n != 0 a null buffer; open with h_out overlapping the range of h_pkt that the packets touch (host addresses: checked
+ * exactly); MAPPED forced with an unmapped buffer; a buffer mapped only in part; on COPY a packet longer than slice_bytes.
+ * n == 0 returns 0. */
+int ptls_hip_pipeline_quic_seal(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                const ptls_hip_quic_packet_t *pkts, size_t n, const void *h_in, void *h_pkt);
+int ptls_hip_pipeline_quic_open(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                const ptls_hip_quic_packet_t *pkts, size_t n, void *h_pkt, void *h_out, uint64_t *h_result,
+                                uint64_t *h_pn_out);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
