@@ -10,6 +10,8 @@
  *   batch.cpp          batches and the device-resident seal / open / header-protection calls
  *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
+ *   quic_parse.cpp     QUIC datagrams parsed on the device into the packet descriptors of quic.cpp, and the connection-ID map
+ *                      (kernels: quic_parse_kernel.hip; the walk and the map arithmetic shared with the CPU check: quic_parse.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
  *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)

@@ -241,6 +241,35 @@ int launch_quic_protect(const ptls_hip_quic_packet_t *pkts, uint32_t n, uint8_t 
  * bytes, read from the packets at pkt */
 int launch_quic_pack_headers(const ptls_hip_quic_packet_t *pkts, uint32_t n, const uint8_t *pkt, void *packed, void *stream);
 
+/* ---- QUIC datagram parsing (quic_parse_kernel.hip; the arithmetic shared with the host and the CPU check: quic_parse.h) ---- */
+
+struct QuicCidEntry; /* quic_parse.h */
+
+/* the counts of one scan workgroup: 256 threads x 8.  Level 0 holds one count per datagram, level k + 1 one sum per
+ * QP_SCAN_SPAN entries of level k; n < 2^32 datagrams need at most three levels */
+constexpr uint32_t QP_SCAN_SPAN = 2048;
+
+struct QuicParseArgs {
+    const ptls_hip_quic_datagram_t *dgrams;
+    uint32_t n;
+    uint32_t short_cid_len, max_per_dgram, require_fixed_bit;
+    const uint8_t *buf;
+    uint32_t *l0;       /* count pass: entries of datagram i; after the scans: their exclusive prefix within the span of i */
+    const uint32_t *l1; /* write pass: exclusive prefix of the span sums within their span (nullptr: a single span) */
+    const uint32_t *l2; /* ... and of the sums of those (nullptr: at most QP_SCAN_SPAN spans) */
+    const QuicCidEntry *table; /* the connection-ID map, or nullptr */
+    uint32_t table_size;
+    const uint64_t *expected_pn;
+    uint64_t expected_count;
+    ptls_hip_quic_packet_t *pkts; /* write pass: the dense outputs */
+    ptls_hip_quic_pktinfo_t *info;
+};
+
+int launch_quic_parse_count(const QuicParseArgs &a, unsigned grid, void *stream);
+/* v[0 .. n) -> the exclusive prefix sums within each span of QP_SCAN_SPAN; sums[s] = the total of span s */
+int launch_quic_parse_scan(uint32_t *v, uint32_t n, uint32_t *sums, unsigned grid, void *stream);
+int launch_quic_parse_write(const QuicParseArgs &a, unsigned grid, void *stream);
+
 /* ---- QUIC key derivation (quic_keys.hip; the arithmetic shared with the CPU check: quic_keys.h) ---- */
 
 /* the HMAC-SHA256 pad states of the Initial salt (quic_keys.h HkPads<HkSha256>), hashed on the host once per call */

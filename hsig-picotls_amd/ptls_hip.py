@@ -37,6 +37,17 @@ QUIC_UNPROTECTED = 1
 QUIC_LABELS_V1, QUIC_LABELS_V2 = 1, 2  # "quic ..." (RFC 9001) / "quicv2 ..." (RFC 9369) key-derivation labels
 QUIC_DCID_STRIDE = 20  # bytes per connection ID passed to ptls_hip_keyset_set_quic_initial
 QUIC_V1_SALT = bytes.fromhex("38762cf7f55934b34d179ae6a4c80cadccbb7f0a")  # RFC 9001 §5.2; the library has no salt built in
+QUIC_DATAGRAM_DTYPE = np.dtype([("off", "<u8"), ("len", "<u4"), ("reserved", "<u4")])
+assert QUIC_DATAGRAM_DTYPE.itemsize == 16
+QUIC_PKTINFO_DTYPE = np.dtype([("dgram", "<u4"), ("version", "<u4"), ("conn", "<u4"), ("token_len", "<u4"), ("dcid_off", "<u2"),
+                               ("scid_off", "<u2"), ("token_off", "<u2"), ("dcid_len", "u1"), ("scid_len", "u1"), ("type", "u1"),
+                               ("status", "u1"), ("flags", "u1"), ("pad", "u1", (5,))])
+assert QUIC_PKTINFO_DTYPE.itemsize == 32
+(QUIC_TYPE_INITIAL, QUIC_TYPE_ZERO_RTT, QUIC_TYPE_HANDSHAKE, QUIC_TYPE_RETRY, QUIC_TYPE_ONE_RTT, QUIC_TYPE_VERSION_NEGOTIATION,
+ QUIC_TYPE_UNKNOWN_VERSION, QUIC_TYPE_NONE) = range(8)
+(QUIC_STATUS_OK, QUIC_STATUS_TRUNCATED, QUIC_STATUS_TOO_SHORT, QUIC_STATUS_BAD_CID_LEN, QUIC_STATUS_BAD_FIXED_BIT) = range(5)
+QUIC_INFO_MORE = 1
+QUIC_NO_CONN = 0xFFFFFFFF
 EINVAL = -1
 
 
@@ -95,6 +106,13 @@ SIGNATURES = {
     "ptls_hip_keyset_set_quic_secrets": (_i, [_vp, _vp, _sz, _sz, _vp, _sz, _i, _vp]),
     "ptls_hip_keyset_update_quic_secrets": (_i, [_vp, _sz, _sz, _vp, _sz, _i, _vp]),
     "ptls_hip_keyset_set_quic_initial": (_i, [_vp, _vp, _sz, _sz, _vp, _vp, _vp, _sz, _i, _vp]),
+    "ptls_hip_quic_cidmap_new": (_vp, [_vp, _sz]),
+    "ptls_hip_quic_cidmap_free": (None, [_vp]),
+    "ptls_hip_quic_cidmap_size": (_sz, [_vp]),
+    "ptls_hip_quic_cidmap_set": (_i, [_vp, _sz, _vp, _vp, _vp, _vp]),
+    "ptls_hip_quic_cidmap_remove": (_i, [_vp, _sz, _vp, _vp, _vp]),
+    "ptls_hip_quic_parse_datagrams": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, ctypes.POINTER(_sz), _vp]),
+    "ptls_hip_quic_parse_timing": (None, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -462,6 +480,69 @@ class QuicBatch:
         if self.ptr:
             lib().ptls_hip_quic_batch_free(self.ptr)
             self.ptr = None
+
+
+class QuicParseParams(ctypes.Structure):
+    """ptls_hip_quic_parse_params_t"""
+    _fields_ = [("short_cid_len", ctypes.c_uint32), ("max_per_dgram", ctypes.c_uint32), ("require_fixed_bit", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("d_expected_pn", ctypes.c_void_p), ("expected_count", ctypes.c_size_t)]
+
+
+def _pack_cids(cids):
+    cids = [bytes(c) for c in cids]
+    assert all(len(c) <= 255 for c in cids)
+    return b"".join(c[:QUIC_DCID_STRIDE].ljust(QUIC_DCID_STRIDE, b"\0") for c in cids), bytes(len(c) for c in cids)
+
+
+class QuicCidMap:
+    """the device-resident Destination Connection ID -> connection map of ptls_hip_quic_parse_datagrams
+    (ptls_hip_quic_cidmap_*): cids are bytes of 0..20 each, conns uint32 values other than QUIC_NO_CONN"""
+
+    def __init__(self, engine, capacity):
+        self.engine = engine
+        self.ptr = lib().ptls_hip_quic_cidmap_new(engine.ptr, capacity)
+        if not self.ptr:
+            raise HipError(f"ptls_hip_quic_cidmap_new: {last_error()}")
+
+    def __len__(self):
+        return lib().ptls_hip_quic_cidmap_size(self.ptr)
+
+    def set(self, cids, conns, stream=None):
+        """insert or replace"""
+        packed, lens = _pack_cids(cids)
+        conns = np.ascontiguousarray(conns, dtype=np.uint32)
+        assert len(conns) == len(lens)
+        _check(lib().ptls_hip_quic_cidmap_set(self.ptr, len(lens), packed, lens, conns.ctypes.data, _stream(stream)),
+               "quic_cidmap_set")
+
+    def remove(self, cids, stream=None):
+        packed, lens = _pack_cids(cids)
+        _check(lib().ptls_hip_quic_cidmap_remove(self.ptr, len(lens), packed, lens, _stream(stream)), "quic_cidmap_remove")
+
+    def close(self):
+        if self.ptr:
+            lib().ptls_hip_quic_cidmap_free(self.ptr)
+            self.ptr = None
+
+
+def quic_parse_datagrams(engine, dgrams, d_buf, buf_len, cidmap=None, short_cid_len=0, max_per_dgram=16, require_fixed_bit=1,
+                         expected_pn=None, expected_count=None, cap=None, stream=None):
+    """ptls_hip_quic_parse_datagrams: dgrams = host numpy array (QUIC_DATAGRAM_DTYPE) of datagrams in the device buffer d_buf;
+    returns (pkts, info), numpy arrays of QUIC_PACKET_DTYPE / QUIC_PKTINFO_DTYPE, one entry per packet.  expected_pn = device
+    tensor of uint64 [3 * conn + space] or None.  cap=None sizes the arrays for the worst case (max_per_dgram per datagram)."""
+    dgrams = np.ascontiguousarray(dgrams, dtype=QUIC_DATAGRAM_DTYPE)
+    if cap is None:
+        cap = len(dgrams) * max_per_dgram
+    if expected_count is None:
+        expected_count = expected_pn.numel() if expected_pn is not None else 0
+    params = QuicParseParams(short_cid_len, max_per_dgram, require_fixed_bit, 0, _ptr(expected_pn), expected_count)
+    pkts, info = np.zeros(cap, dtype=QUIC_PACKET_DTYPE), np.zeros(cap, dtype=QUIC_PKTINFO_DTYPE)
+    n_pkts = ctypes.c_size_t(0)
+    _check(lib().ptls_hip_quic_parse_datagrams(engine.ptr, ctypes.addressof(params), cidmap.ptr if cidmap is not None else None,
+                                               dgrams.ctypes.data, len(dgrams), _ptr(d_buf), buf_len, pkts.ctypes.data,
+                                               info.ctypes.data, cap, ctypes.byref(n_pkts), _stream(stream)),
+           "quic_parse_datagrams")
+    return pkts[:n_pkts.value], info[:n_pkts.value]
 
 
 def partition_bytes(recs, parts):

@@ -512,9 +512,11 @@ ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *batch);
  * QUIC batch must therefore be ordered: on the same stream, or by the caller's own synchronisation.
  *
  * Packets in host memory go through the host pipelines with ptls_hip_pipeline_quic_seal / _open (2g).
- * Out of scope: the node API (2d); splitting coalesced datagrams and parsing long-header fields
- * (the caller supplies pn_offset); Retry and Version Negotiation packets (they carry no packet protection); choosing the
- * key by key phase on the device (the AES planner needs every packet's key slot on the host). */
+ * Received datagrams are split into these descriptors on the device by ptls_hip_quic_parse_datagrams (2h): coalesced
+ * packets, the long-header fields up to pn_offset and pkt_len, and the key slot from the Destination Connection ID.
+ * Out of scope: the node API (2d); handling Retry and Version Negotiation packets (they carry no packet protection; 2h
+ * reports them and the host answers); choosing the key by key phase on the device (the AES planner needs every packet's
+ * key slot on the host). */
 int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
                              void *pkt, void *stream);
 int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, void *pkt, void *out,
@@ -601,6 +603,129 @@ int ptls_hip_pipeline_quic_seal(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, p
 int ptls_hip_pipeline_quic_open(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
                                 const ptls_hip_quic_packet_t *pkts, size_t n, void *h_pkt, void *h_out, uint64_t *h_result,
                                 uint64_t *h_pn_out);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2h. QUIC datagrams parsed on the device: coalesced packets, long headers, connection-ID lookup  *
+ *     (RFC 8999, RFC 9000 §12.2, §16, §17, RFC 9369 §3.2)                                         *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The receive side in front of 2e: UDP datagrams in device memory go in, the packet descriptors of 2e come out, ready for
+ * ptls_hip_quic_batch_new(..., open = 1), each with an info record.  The host still plans the open batch (40 + 32 bytes per
+ * packet come back instead of the packets) and decides what to do with Retry, Version Negotiation and unknown-version
+ * packets. */
+
+#define PTLS_HIP_QUIC_TYPE_INITIAL 0u
+#define PTLS_HIP_QUIC_TYPE_ZERO_RTT 1u
+#define PTLS_HIP_QUIC_TYPE_HANDSHAKE 2u
+#define PTLS_HIP_QUIC_TYPE_RETRY 3u
+#define PTLS_HIP_QUIC_TYPE_ONE_RTT 4u
+#define PTLS_HIP_QUIC_TYPE_VERSION_NEGOTIATION 5u
+#define PTLS_HIP_QUIC_TYPE_UNKNOWN_VERSION 6u /* a long header of a version other than 0, 1 and 0x6b3343cf */
+#define PTLS_HIP_QUIC_TYPE_NONE 7u            /* a long header cut off before its version */
+#define PTLS_HIP_QUIC_STATUS_OK 0u
+#define PTLS_HIP_QUIC_STATUS_TRUNCATED 1u     /* a header field, the token or Length reaches past the datagram's end */
+#define PTLS_HIP_QUIC_STATUS_TOO_SHORT 2u     /* less than 20 bytes behind pn_offset: no room for the header-protection sample */
+#define PTLS_HIP_QUIC_STATUS_BAD_CID_LEN 3u   /* a connection-ID length above 20 under version 1 or 2 */
+#define PTLS_HIP_QUIC_STATUS_BAD_FIXED_BIT 4u /* the fixed bit (0x40) is clear and require_fixed_bit is set */
+#define PTLS_HIP_QUIC_INFO_MORE 1u            /* flags: the datagram holds bytes behind this, its max_per_dgram-th, entry */
+#define PTLS_HIP_QUIC_NO_CONN 0xffffffffu
+
+/* The connection-ID map: Destination Connection ID (0..20 bytes; the empty one is a valid key) -> connection number, which
+ * the parse call writes into `key`, `hp_key` and `conn`.  Resident on the device as an open-addressing table of 32-byte
+ * entries with linear probing, sized to the next power of two >= 2 * capacity (load <= 0.5); the host keeps the
+ * authoritative mirror, removes with a backward shift (no tombstones) and uploads what changed.  The device only reads it.
+ * cids = count connection IDs at a 20-byte stride in host memory, cid_lens[i] = 0..20, as in 2f.
+ * set inserts or replaces; remove of an absent CID is not an error.  Both are synchronous like
+ * ptls_hip_keyset_set_quic_secrets and must not run concurrently with each other or with a parse call on the same map.
+ * PTLS_HIP_EINVAL with a message and nothing changed for a null pointer (cids / cid_lens / conns with count != 0), a
+ * cid_lens[i] above 20, a conns[i] of PTLS_HIP_QUIC_NO_CONN, or a set after which the map would hold more than `capacity`
+ * CIDs; cidmap_new: NULL for a null engine or a capacity outside 1 .. 2^30.  cidmap_free waits for the parse calls that
+ * used the map. */
+typedef struct st_ptls_hip_quic_cidmap_t ptls_hip_quic_cidmap_t;
+ptls_hip_quic_cidmap_t *ptls_hip_quic_cidmap_new(ptls_hip_engine_t *engine, size_t capacity);
+void ptls_hip_quic_cidmap_free(ptls_hip_quic_cidmap_t *map);
+size_t ptls_hip_quic_cidmap_size(ptls_hip_quic_cidmap_t *map); /* CIDs in the map */
+int ptls_hip_quic_cidmap_set(ptls_hip_quic_cidmap_t *map, size_t count, const void *cids, const uint8_t *cid_lens,
+                             const uint32_t *conns, void *stream);
+int ptls_hip_quic_cidmap_remove(ptls_hip_quic_cidmap_t *map, size_t count, const void *cids, const uint8_t *cid_lens,
+                                void *stream);
+
+typedef struct st_ptls_hip_quic_datagram_t { /* 16 bytes */
+    uint64_t off;      /* first byte of the datagram in d_buf */
+    uint32_t len;      /* <= 65535; 0 = no entry */
+    uint32_t reserved;
+} ptls_hip_quic_datagram_t;
+
+typedef struct st_ptls_hip_quic_pktinfo_t { /* 32 bytes; entry k describes packet descriptor k */
+    uint32_t dgram;     /* index of the datagram the packet came in */
+    uint32_t version;   /* long headers; 0 for a short header */
+    uint32_t conn;      /* the map's value for the DCID, or PTLS_HIP_QUIC_NO_CONN */
+    uint32_t token_len; /* Initial */
+    uint16_t dcid_off, scid_off, token_off; /* from the packet's first byte; 0 = the field was not reached or does not exist */
+    uint8_t dcid_len, scid_len;
+    uint8_t type;       /* PTLS_HIP_QUIC_TYPE_* */
+    uint8_t status;     /* PTLS_HIP_QUIC_STATUS_* */
+    uint8_t flags;      /* PTLS_HIP_QUIC_INFO_MORE */
+    uint8_t pad[5];     /* 0 */
+} ptls_hip_quic_pktinfo_t;
+
+typedef struct st_ptls_hip_quic_parse_params_t {
+    uint32_t short_cid_len;        /* 0..20: the length of the DCIDs this endpoint issued (short headers do not carry it) */
+    uint32_t max_per_dgram;        /* 1..16: entries per datagram */
+    uint32_t require_fixed_bit;    /* != 0: a clear fixed bit is an error; 0: the bit is not looked at (RFC 9287) */
+    uint32_t reserved;             /* 0 */
+    const uint64_t *d_expected_pn; /* device: expected packet number of connection c, space s at [3 c + s], or NULL */
+    size_t expected_count;         /* entries of d_expected_pn */
+} ptls_hip_quic_parse_params_t;
+
+/* Walks the n datagrams dgrams[i] (a HOST array) in the device buffer d_buf (buf_len bytes) and writes one
+ * ptls_hip_quic_packet_t and one ptls_hip_quic_pktinfo_t per entry into the HOST arrays h_pkts and h_info (cap entries each).
+ * Synchronous: on return `stream` has been synchronised and the entries are in the host arrays.  Entries are dense, in
+ * datagram order and within a datagram in wire order; the same input gives the same bytes; exactly *n_pkts entries are
+ * written and nothing past them.  No byte at or past a datagram's end is read.
+ *
+ * The walk of one packet, with `rest` = the bytes from its first byte to the datagram's end:
+ *   short header (first & 0x80 == 0): type ONE_RTT; dcid_off 1, dcid_len short_cid_len, pn_offset = 1 + short_cid_len; the
+ *     packet takes the rest of the datagram (RFC 9000 §12.2); rest < pn_offset + 20 is TOO_SHORT.
+ *   long header: version (big-endian at 1), DCID length at 5, the DCID, the SCID length, the SCID; a field past the
+ *     datagram's end is TRUNCATED.  Version 0 is VERSION_NEGOTIATION, a version other than 1 and 0x6b3343cf is
+ *     UNKNOWN_VERSION: both take the rest of the datagram, with DCID and SCID (up to 255 bytes) by the invariants of RFC 8999.
+ *     Version 1 has the type bits Initial 0, 0-RTT 1, Handshake 2, Retry 3; version 0x6b3343cf those of RFC 9369 §3.2: Retry
+ *     0, Initial 1, 0-RTT 2, Handshake 3.  Under these two a CID length above 20 is BAD_CID_LEN; Retry takes the rest of the
+ *     datagram; Initial carries the token-length varint and the token; Initial, 0-RTT and Handshake carry the Length varint
+ *     (any of the four widths, non-minimal encodings included), pn_offset is the first byte behind it and
+ *     pkt_len = pn_offset + Length; Length < 20 is TOO_SHORT, pn_offset + Length > rest is TRUNCATED.
+ *   With require_fixed_bit, a short packet or a long one of version 1 or 0x6b3343cf with first & 0x40 == 0 is BAD_FIXED_BIT
+ *     (checked before the lengths).
+ *   Every status but OK ends the datagram: the entry covers the rest of it, with pn_offset 0; the info fields reached before
+ *   the error stand, the others are 0.  Retry, Version Negotiation and unknown-version entries have status OK and pn_offset 0.
+ *   An entry is openable if and only if pn_offset != 0; then pkt_len >= pn_offset + 20, so ptls_hip_quic_batch_new takes it.
+ * A zero-length datagram gives no entry.  A datagram with more than max_per_dgram entries: its last entry carries
+ * PTLS_HIP_QUIC_INFO_MORE and the rest is dropped.  The RFC 9000 §12.2 rule that later coalesced packets with another DCID
+ * are ignored is the host's: it sees the conn of each entry.
+ *
+ * Each packet descriptor: pkt_off = the absolute offset in d_buf; pkt_len, pn_offset from the walk;
+ * data_off = pkt_off + pn_offset + 1 (with the open call's `out` a separate buffer of d_buf's size, the plaintext areas are
+ * pairwise disjoint by construction); pn_len = 0, flags = 0; key = hp_key = conn = the map's value for the DCID
+ * (status OK and dcid_len <= 20) or PTLS_HIP_QUIC_NO_CONN (no match, or map == NULL), which the open call refuses by name as
+ * a key slot outside the keyset; pn = d_expected_pn[3 conn + space] with space 0 for Initial, 1 for Handshake, 2 for 0-RTT and
+ * 1-RTT, when the entry is openable, the table is not NULL, a connection matched and the index is below expected_count,
+ * else 0.
+ *
+ * PTLS_HIP_EINVAL with a message, nothing launched and nothing written (except *n_pkts where stated): a null engine,
+ * params or n_pkts, or with n != 0 a null dgrams or d_buf, or with cap != 0 a null h_pkts or h_info; n > 2^32 - 1 or
+ * n * max_per_dgram > 2^32 - 1; a datagram with len > 65535 or off + len > buf_len (the message names its index);
+ * short_cid_len above 20, max_per_dgram outside 1..16 or reserved != 0; a map of another engine.  cap smaller than the
+ * number of entries: PTLS_HIP_EINVAL after the counting pass, *n_pkts = the number needed, the host arrays untouched (cap = 0
+ * is the sizing call).  n == 0 returns 0 with *n_pkts = 0. */
+int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *engine, const ptls_hip_quic_parse_params_t *params,
+                                  ptls_hip_quic_cidmap_t *map, const ptls_hip_quic_datagram_t *dgrams, size_t n,
+                                  const void *d_buf, size_t buf_len, ptls_hip_quic_packet_t *h_pkts,
+                                  ptls_hip_quic_pktinfo_t *h_info, size_t cap, size_t *n_pkts, void *stream);
+/* Diagnostic (tools/bench_quic_parse.py): enable != 0 makes the calling thread's parse calls time themselves with HIP events;
+ * kernels_ms / d2h_ms (either may be NULL) receive the last such call's kernel time (upload of the datagram array, count,
+ * scan and write passes) and the time of the copies of the entries back to the host. */
+void ptls_hip_quic_parse_timing(int enable, float *kernels_ms, float *d2h_ms);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
