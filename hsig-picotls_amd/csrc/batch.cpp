@@ -179,15 +179,39 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
         return fail(PTLS_HIP_EINVAL, "seal/open: a record names key slot %u, the keyset has %zu", b->max_key, ks->nslots);
     if (in == nullptr || out == nullptr || (open && result == nullptr))
         return fail(PTLS_HIP_EINVAL, "seal/open: null buffer");
-    DeviceGuard g(b->eng->device);
+    LaunchPlan p{};
+    p.eng = b->eng;
+    p.n = b->n;
+    p.d_recs = b->d_recs;
+    p.d_recs_ord = b->d_recs_ord;
+    p.d_order = b->d_order;
+    p.d_chunks = b->d_chunks;
+    p.nchunks = b->nchunks;
+    p.lanes = b->lanes;
+    p.wg = b->wg;
+    p.chacha_lanes = b->chacha_lanes;
+    p.all_aligned = b->all_aligned;
+    p.ncus = batch_cus(b);
+    p.d_clk = b->d_clk;
+    p.clk_bytes = b->clk_bytes;
+    if (int e = run_plan(p, ks, in, aad, out, result, stream, open, hp_ks, supp, mask))
+        return e;
+    b->uses.note(stream);
+    return 0;
+}
+
+int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result, void *stream,
+             bool open, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, void *mask)
+{
+    DeviceGuard g(p.eng->device);
     const uint8_t *in8 = static_cast<const uint8_t *>(in), *aad8 = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
-    const bool aligned = b->all_aligned && ((reinterpret_cast<uintptr_t>(in8) | reinterpret_cast<uintptr_t>(aad8) |
-                                             reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    const bool aligned = p.all_aligned && ((reinterpret_cast<uintptr_t>(in8) | reinterpret_cast<uintptr_t>(aad8) |
+                                            reinterpret_cast<uintptr_t>(out)) & 15) == 0;
     int e;
     if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305) {
         ChaChaArgs a{};
-        a.recs = b->d_recs; /* descriptor order: no key runs, no chunks */
-        a.n = b->n;
+        a.recs = p.d_recs; /* descriptor order: no key runs, no chunks */
+        a.n = p.n;
         a.in = in8;
         a.aad = aad8;
         a.out = static_cast<uint8_t *>(out);
@@ -197,34 +221,33 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
         a.hp_slots = hp_ks != nullptr ? hp_ks->d_chacha : nullptr;
         a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
         a.mask = static_cast<uint8_t *>(mask);
-        e = launch_chacha_batch(b->chacha_lanes, open, stream, a, aligned);
+        e = launch_chacha_batch(p.chacha_lanes, open, stream, a, aligned);
     } else {
         KernelArgs a{};
-        a.recs = b->d_recs;
-        a.recs_ord = b->d_recs_ord != nullptr ? b->d_recs_ord : b->d_recs;
-        a.order = b->d_order;
-        a.chunks = b->d_chunks;
-        a.nchunks = b->nchunks;
+        a.recs = p.d_recs;
+        a.recs_ord = p.d_recs_ord != nullptr ? p.d_recs_ord : p.d_recs;
+        a.order = p.d_order;
+        a.chunks = p.d_chunks;
+        a.nchunks = p.nchunks;
         a.in = in8;
         a.aad = aad8;
         a.out = static_cast<uint8_t *>(out);
         a.result = result;
-        set_key_args(a, b->eng, ks, hp_ks);
+        set_key_args(a, p.eng, ks, hp_ks);
         a.supp = supp;
         a.mask = static_cast<uint8_t *>(mask);
-        const unsigned grid = plan_grid(b->n, b->nchunks, b->lanes, batch_cus(b));
-        if (b->d_clk != nullptr && b->clk_bytes < (size_t)grid * 32)
+        const unsigned grid = plan_grid(p.n, p.nchunks, p.lanes, p.ncus);
+        if (p.d_clk != nullptr && p.clk_bytes < (size_t)grid * 32)
             return fail(PTLS_HIP_EINVAL, "seal/open: the clock-stamp buffer is smaller than 32 bytes x %u workgroups", grid);
-        a.clk = b->d_clk;
-        a.clk_bytes = b->clk_bytes;
-        a.queue = queue_slot(b->eng);
-        e = launch_batch(b->lanes, ks->key_size == 16 ? 10 : 14, open, b->wg, grid, stream, a, aligned);
+        a.clk = p.d_clk;
+        a.clk_bytes = p.clk_bytes;
+        a.queue = queue_slot(p.eng);
+        e = launch_batch(p.lanes, ks->key_size == 16 ? 10 : 14, open, p.wg, grid, stream, a, aligned);
     }
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     keyset_note_use(ks, stream);
     keyset_note_use(hp_ks, stream);
-    b->uses.note(stream);
     return 0;
 }
 

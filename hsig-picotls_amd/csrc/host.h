@@ -12,6 +12,8 @@
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
  *   quic_parse.cpp     QUIC datagrams parsed on the device into the packet descriptors of quic.cpp, and the connection-ID map
  *                      (kernels: quic_parse_kernel.hip; the walk and the map arithmetic shared with the CPU check: quic_parse.h)
+ *   quic_rx.cpp        the QUIC receive object: parsed entries kept on the device, selected, packed, planned and opened there
+ *                      (kernels: quic_rx_kernel.hip; the select rule and the sums' terms shared with the CPU check: quic_rx.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
  *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)
@@ -29,6 +31,7 @@
 
 #include <atomic>
 #include <cstdint>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -226,6 +229,9 @@ uint32_t *queue_slot(ptls_hip_engine_t *e);
 /* ---- planner.cpp ---- */
 int choose_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu);
 int choose_chacha_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu);
+/* the same rules over the sums the two functions above take (n != 0) */
+int choose_lanes_from(double sum, size_t n, size_t runs, unsigned ncu);
+int choose_chacha_lanes_from(double sum, size_t n, unsigned ncu);
 unsigned plan_grid(size_t n, size_t nchunks, int lanes, unsigned ncu);
 int plan_wg(const std::vector<Chunk> &ch, int lanes);
 void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned ncu, std::vector<Chunk> &ch,
@@ -325,6 +331,53 @@ int plan_quic_slice(const ptls_hip_quic_packet_t *pkts, const ptls_hip_record_t 
 int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result,
               void *stream, bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr,
               void *mask = nullptr, int algo = 0);
+
+/* what one seal / open launch reads of a plan, wherever the plan was made: a batch's (run_batch), or the device-made one of
+ * the QUIC receive step (quic_rx.cpp), which has no ptls_hip_batch_t and no host mirror of its descriptors */
+struct LaunchPlan {
+    ptls_hip_engine_t *eng;
+    size_t n;
+    const ptls_hip_record_t *d_recs;
+    const ptls_hip_record_t *d_recs_ord; /* plan order, or nullptr: d_recs serves as both and d_order is nullptr */
+    const uint32_t *d_order;
+    const Chunk *d_chunks;
+    uint32_t nchunks;
+    int lanes, wg, chacha_lanes;
+    bool all_aligned;
+    unsigned ncus;   /* CUs the launch is sized for (batch_cus) */
+    uint64_t *d_clk; /* diagnostic clock stamps, or nullptr */
+    size_t clk_bytes;
+};
+/* the launch of run_batch behind its refusals: n != 0, non-null buffers, every key slot inside the keyset.  Notes the use
+ * of the keysets; the caller notes the use of whatever owns the plan */
+int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result, void *stream,
+             bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr, void *mask = nullptr);
+
+/* ---- quic_parse.cpp: the steps of the parse call, shared with the receive object of quic_rx.cpp ---- */
+/* the levels of an exclusive scan over n counts (launch_quic_parse_scan), laid out in one allocation of `words` uint32 */
+struct ScanLevels {
+    uint32_t *l0, *l1, *l2, *total; /* the counts, the span sums (has1), their span sums (has2), the grand total */
+    size_t n, n1, n2, words;
+    bool has1, has2;
+};
+ScanLevels scan_levels(uint32_t *base, size_t n); /* base == nullptr: for `words` alone */
+int launch_scan_levels(const ScanLevels &L, int ncu, void *stream);
+unsigned quic_scan_grid(size_t items, int ncu);
+/* the refusals of ptls_hip_quic_parse_datagrams behind its null-pointer checks */
+int quic_parse_check(const char *who, ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
+                     const ptls_hip_quic_datagram_t *dgrams, size_t n, size_t buf_len);
+/* n != 0: uploads the datagram array into d_dgrams, counts and scans into d_levels (scan_levels(n).words uint32), reads the
+ * number of entries back into *total (synchronises the stream); mark(0) / mark(1) are called around the device work */
+int quic_parse_count(const char *who, ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
+                     const ptls_hip_quic_datagram_t *dgrams, size_t n, const void *d_buf, void *d_dgrams, uint32_t *d_levels,
+                     void *stream, QuicParseArgs &a, unsigned *walk_grid, uint32_t *total, const std::function<void(int)> &mark);
+/* the write pass of the entries counted by quic_parse_count into device arrays of *total entries */
+int quic_parse_write(const char *who, ptls_hip_quic_cidmap_t *map, QuicParseArgs &a, unsigned walk_grid, ptls_hip_quic_packet_t *d_pkts,
+                     ptls_hip_quic_pktinfo_t *d_info, void *stream);
+
+/* ---- quic.cpp ---- */
+/* the lanes the inner batch of a QUIC batch was planned with (the AES batch kernel's, the ChaCha kernel's) */
+void quic_batch_lanes(ptls_hip_quic_batch_t *q, int *lanes, int *chacha_lanes);
 
 /* ---- plugin_worker.cpp ---- */
 /* ptls_hip_keyset_free of a plugin context's pooled slot */

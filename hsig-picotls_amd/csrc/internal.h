@@ -270,6 +270,39 @@ int launch_quic_parse_count(const QuicParseArgs &a, unsigned grid, void *stream)
 int launch_quic_parse_scan(uint32_t *v, uint32_t n, uint32_t *sums, unsigned grid, void *stream);
 int launch_quic_parse_write(const QuicParseArgs &a, unsigned grid, void *stream);
 
+/* ---- the device-side receive step (quic_rx_kernel.hip; the arithmetic shared with the host and the CPU check: quic_rx.h) ---- */
+
+struct QuicRxLimits; /* quic_rx.h */
+
+/* packets of one sort tile: 256 threads x 4.  Each of a tile's four waves takes 256 consecutive packets in four rounds of
+ * 64, so a wave's packets are in entry order by (round, lane) */
+constexpr uint32_t QRX_TILE = 1024;
+
+struct QuicRxArgs {
+    const ptls_hip_quic_packet_t *pkts;  /* the loaded entries */
+    const ptls_hip_quic_pktinfo_t *info; /* or nullptr */
+    uint32_t n;
+    /* the scan levels over the select flags (l0: flag, then exclusive prefix within the span; l1 / l2 as in QuicParseArgs) */
+    uint32_t *l0;
+    const uint32_t *l1, *l2;
+    const uint32_t *total;          /* the number of selected entries, once the scans have run */
+    uint32_t *sel;                  /* compact: entry index of the j-th selected packet (the caller's d_sel) */
+    ptls_hip_quic_packet_t *packed; /* compact: its descriptor */
+    uint32_t *keys;                 /* compact: its sort key (quic_rx_sort_key) */
+    uint64_t *stats;                /* QRX_NSTATS sums over the selected packets: zeroed by the select pass */
+    Chunk *chunk;                   /* stats: the sparse kernel's single chunk {0, m, 0xffffffff, 0} */
+};
+
+int launch_quic_rx_select(const QuicRxArgs &a, const QuicRxLimits &lim, unsigned grid, void *stream);
+int launch_quic_rx_compact(const QuicRxArgs &a, const QuicRxLimits &lim, unsigned grid, void *stream);
+int launch_quic_rx_stats(const QuicRxArgs &a, unsigned grid, void *stream);
+/* One radix pass over m positions, digit = (keys[v] >> shift) & 63 with v = src[t] (src == nullptr: v = t).  hist: the
+ * [digit][tile] counts (64 * ntiles words, ntiles = ceil(m / QRX_TILE)); scatter, after their exclusive scan into hl0 / hl1 /
+ * hl2: dst[position] = v, stable */
+int launch_quic_rx_hist(const uint32_t *keys, const uint32_t *src, uint32_t m, uint32_t shift, uint32_t *hist, void *stream);
+int launch_quic_rx_scatter(const uint32_t *keys, const uint32_t *src, uint32_t m, uint32_t shift, const uint32_t *hl0,
+                           const uint32_t *hl1, const uint32_t *hl2, uint32_t *dst, void *stream);
+
 /* ---- QUIC key derivation (quic_keys.hip; the arithmetic shared with the CPU check: quic_keys.h) ---- */
 
 /* the HMAC-SHA256 pad states of the Initial salt (quic_keys.h HkPads<HkSha256>), hashed on the host once per call */

@@ -30,6 +30,14 @@ int choose_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu)
         if (i != 0 && recs[i].key != recs[i - 1].key)
             ++runs;
     }
+    return choose_lanes_from(sum, n, runs, ncu);
+}
+
+/* the rules over what choose_lanes sums: `sum` GHASH elements in n records (n != 0) of `runs` key runs.  The device-side
+ * receive step (quic_rx.cpp) takes the same sums on the device as integers, which a double holds exactly, and so chooses
+ * what choose_lanes chooses for the same records. */
+int choose_lanes_from(double sum, size_t n, size_t runs, unsigned ncu)
+{
     const double mean = sum / (double)n;
     const double per_run = (double)n / (double)runs;
     /* round 4 (the windowed lane combination for every G, batch_kernel.h WIN_ALL): G = 4 is as fast as G = 8 or faster at
@@ -82,6 +90,12 @@ int choose_chacha_lanes(const ptls_hip_record_t *recs, size_t n, unsigned ncu)
     double sum = 0;
     for (size_t i = 0; i < n; ++i)
         sum += (double)(recs[i].len / 64);
+    return choose_chacha_lanes_from(sum, n, ncu);
+}
+
+/* ... over `sum` whole 64-byte blocks in n records (n != 0), as choose_lanes_from */
+int choose_chacha_lanes_from(double sum, size_t n, unsigned ncu)
+{
     const double blocks = sum / (double)n;
     const double want = 2048.0 * (double)(ncu ? ncu : 256); /* lanes: 8 waves on each of a CU's 4 SIMDs */
     int g = blocks >= 4 ? 4 : 1;

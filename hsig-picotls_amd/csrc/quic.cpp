@@ -112,6 +112,12 @@ extern "C" ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *
     return q->inner;
 }
 
+void quic_batch_lanes(ptls_hip_quic_batch_t *q, int *lanes, int *chacha_lanes)
+{
+    *lanes = q->inner->lanes;
+    *chacha_lanes = q->inner->chacha_lanes;
+}
+
 /* what both calls refuse before anything is launched; `who` is the call's name */
 static int check_call(const char *who, ptls_hip_quic_batch_t *q, bool open, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks)
 {

@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <set>
 #include <string>
 
@@ -211,18 +212,43 @@ unsigned parse_grid(size_t items, int ncu)
 
 } // namespace
 
-extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr,
-                                             ptls_hip_quic_cidmap_t *map, const ptls_hip_quic_datagram_t *dgrams, size_t n,
-                                             const void *d_buf, size_t buf_len, ptls_hip_quic_packet_t *h_pkts,
-                                             ptls_hip_quic_pktinfo_t *h_info, size_t cap, size_t *n_pkts, void *stream)
+/* the scan levels in one allocation: the counts, the span sums, their span sums, and the total */
+ScanLevels scan_levels(uint32_t *base, size_t n)
 {
-    const char *who = "quic_parse_datagrams";
-    if (eng == nullptr || pr == nullptr || n_pkts == nullptr)
-        return fail(PTLS_HIP_EINVAL, "%s: null engine, parameters or n_pkts", who);
-    if (n != 0 && (dgrams == nullptr || d_buf == nullptr))
-        return fail(PTLS_HIP_EINVAL, "%s: null datagram array or buffer", who);
-    if (cap != 0 && (h_pkts == nullptr || h_info == nullptr))
-        return fail(PTLS_HIP_EINVAL, "%s: null output array", who);
+    ScanLevels L{};
+    L.n = n;
+    L.n1 = (n + QP_SCAN_SPAN - 1) / QP_SCAN_SPAN;
+    L.n2 = (L.n1 + QP_SCAN_SPAN - 1) / QP_SCAN_SPAN;
+    L.has1 = L.n1 > 1, L.has2 = L.n2 > 1; /* n2 <= QP_SCAN_SPAN: n < 2^32 */
+    const auto pad4 = [](size_t k) { return (k + 3) & ~(size_t)3; };
+    const size_t o1 = pad4(n), o2 = o1 + pad4(L.has1 ? L.n1 : 0), ot = o2 + pad4(L.has2 ? L.n2 : 0);
+    L.words = ot + 4;
+    L.l0 = base;
+    L.l1 = base + o1;
+    L.l2 = base + o2;
+    L.total = base + ot;
+    return L;
+}
+
+/* one scan launch per level; the top level is a single span whose sum is the total */
+int launch_scan_levels(const ScanLevels &L, int ncu, void *stream)
+{
+    int e = launch_quic_parse_scan(L.l0, (uint32_t)L.n, L.has1 ? L.l1 : L.total, parse_grid(L.n1, ncu), stream);
+    if (e == 0 && L.has1)
+        e = launch_quic_parse_scan(L.l1, (uint32_t)L.n1, L.has2 ? L.l2 : L.total, parse_grid(L.n2, ncu), stream);
+    if (e == 0 && L.has2)
+        e = launch_quic_parse_scan(L.l2, (uint32_t)L.n2, L.total, 1, stream);
+    return e;
+}
+
+unsigned quic_scan_grid(size_t items, int ncu)
+{
+    return parse_grid(items, ncu);
+}
+
+int quic_parse_check(const char *who, ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
+                     const ptls_hip_quic_datagram_t *dgrams, size_t n, size_t buf_len)
+{
     if (pr->short_cid_len > QP_MAX_CID)
         return fail(PTLS_HIP_EINVAL, "%s: short_cid_len %u is above 20", who, pr->short_cid_len);
     if (pr->max_per_dgram < 1 || pr->max_per_dgram > 16)
@@ -240,6 +266,77 @@ extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_
             return fail(PTLS_HIP_EINVAL, "%s: datagram %zu: off %llu + len %u is past the buffer of %zu bytes", who, i,
                         (unsigned long long)dgrams[i].off, dgrams[i].len, buf_len);
     }
+    return 0;
+}
+
+int quic_parse_count(const char *who, ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
+                     const ptls_hip_quic_datagram_t *dgrams, size_t n, const void *d_buf, void *d_dgrams, uint32_t *d_levels,
+                     void *stream, QuicParseArgs &a, unsigned *walk_grid, uint32_t *total, const std::function<void(int)> &mark)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (map != nullptr && map->d_table == nullptr) /* a map nothing was ever set in: the empty table */
+        if (int rc = map_upload(who, map, nullptr, stream))
+            return rc;
+    const ScanLevels L = scan_levels(d_levels, n);
+    a = QuicParseArgs{};
+    a.dgrams = static_cast<const ptls_hip_quic_datagram_t *>(d_dgrams);
+    a.n = (uint32_t)n;
+    a.short_cid_len = pr->short_cid_len;
+    a.max_per_dgram = pr->max_per_dgram;
+    a.require_fixed_bit = pr->require_fixed_bit;
+    a.buf = static_cast<const uint8_t *>(d_buf);
+    a.l0 = L.l0;
+    a.l1 = L.has1 ? L.l1 : nullptr;
+    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.table = map != nullptr ? map->d_table : nullptr;
+    a.table_size = map != nullptr ? (uint32_t)map->table.size() : 0;
+    a.expected_pn = pr->d_expected_pn;
+    a.expected_count = pr->expected_count;
+    *walk_grid = parse_grid((n + 255) / 256, eng->ncu);
+
+    mark(0);
+    HIP_TRY(hipMemcpyAsync(d_dgrams, dgrams, n * sizeof(ptls_hip_quic_datagram_t), hipMemcpyHostToDevice, s), PTLS_HIP_ENODEV);
+    int e = launch_quic_parse_count(a, *walk_grid, stream);
+    if (e == 0)
+        e = launch_scan_levels(L, eng->ncu, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    if (map != nullptr)
+        map->uses.note(stream);
+    mark(1);
+    *total = 0;
+    HIP_TRY(hipMemcpyAsync(total, L.total, sizeof(*total), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
+    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    return 0;
+}
+
+int quic_parse_write(const char *who, ptls_hip_quic_cidmap_t *map, QuicParseArgs &a, unsigned walk_grid, ptls_hip_quic_packet_t *d_pkts,
+                     ptls_hip_quic_pktinfo_t *d_info, void *stream)
+{
+    a.pkts = d_pkts;
+    a.info = d_info;
+    const int e = launch_quic_parse_write(a, walk_grid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    if (map != nullptr)
+        map->uses.note(stream);
+    return 0;
+}
+
+extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr,
+                                             ptls_hip_quic_cidmap_t *map, const ptls_hip_quic_datagram_t *dgrams, size_t n,
+                                             const void *d_buf, size_t buf_len, ptls_hip_quic_packet_t *h_pkts,
+                                             ptls_hip_quic_pktinfo_t *h_info, size_t cap, size_t *n_pkts, void *stream)
+{
+    const char *who = "quic_parse_datagrams";
+    if (eng == nullptr || pr == nullptr || n_pkts == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null engine, parameters or n_pkts", who);
+    if (n != 0 && (dgrams == nullptr || d_buf == nullptr))
+        return fail(PTLS_HIP_EINVAL, "%s: null datagram array or buffer", who);
+    if (cap != 0 && (h_pkts == nullptr || h_info == nullptr))
+        return fail(PTLS_HIP_EINVAL, "%s: null output array", who);
+    if (int rc = quic_parse_check(who, eng, pr, map, dgrams, n, buf_len))
+        return rc;
     if (n == 0) {
         *n_pkts = 0;
         return 0;
@@ -247,53 +344,15 @@ extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_
 
     DeviceGuard g(eng->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (map != nullptr && map->d_table == nullptr) /* a map nothing was ever set in: the empty table */
-        if (int rc = map_upload(who, map, nullptr, stream))
-            return rc;
     ParseScratch sc(eng);
-    /* the scan levels in one allocation: n counts, the span sums, their span sums, and the total */
-    const size_t n1 = (n + QP_SCAN_SPAN - 1) / QP_SCAN_SPAN, n2 = (n1 + QP_SCAN_SPAN - 1) / QP_SCAN_SPAN;
-    const bool has1 = n1 > 1, has2 = n2 > 1; /* n2 <= QP_SCAN_SPAN: n < 2^32 */
-    const auto pad4 = [](size_t k) { return (k + 3) & ~(size_t)3; };
-    const size_t o1 = pad4(n), o2 = o1 + pad4(has1 ? n1 : 0), ot = o2 + pad4(has2 ? n2 : 0);
     HIP_TRY(dev_alloc(eng, &sc.d_dgrams, n * sizeof(ptls_hip_quic_datagram_t)), PTLS_HIP_ENOMEM);
-    HIP_TRY(dev_alloc(eng, &sc.d_levels, (ot + 4) * sizeof(uint32_t)), PTLS_HIP_ENOMEM);
-    uint32_t *l0 = static_cast<uint32_t *>(sc.d_levels), *l1 = l0 + o1, *l2 = l0 + o2, *d_total = l0 + ot;
-
+    HIP_TRY(dev_alloc(eng, &sc.d_levels, scan_levels(nullptr, n).words * sizeof(uint32_t)), PTLS_HIP_ENOMEM);
     QuicParseArgs a{};
-    a.dgrams = static_cast<const ptls_hip_quic_datagram_t *>(sc.d_dgrams);
-    a.n = (uint32_t)n;
-    a.short_cid_len = pr->short_cid_len;
-    a.max_per_dgram = pr->max_per_dgram;
-    a.require_fixed_bit = pr->require_fixed_bit;
-    a.buf = static_cast<const uint8_t *>(d_buf);
-    a.l0 = l0;
-    a.l1 = has1 ? l1 : nullptr;
-    a.l2 = has2 ? l2 : nullptr;
-    a.table = map != nullptr ? map->d_table : nullptr;
-    a.table_size = map != nullptr ? (uint32_t)map->table.size() : 0;
-    a.expected_pn = pr->d_expected_pn;
-    a.expected_count = pr->expected_count;
-    const unsigned walk_grid = parse_grid((n + 255) / 256, eng->ncu);
-
-    sc.mark(0, s);
-    HIP_TRY(hipMemcpyAsync(sc.d_dgrams, dgrams, n * sizeof(ptls_hip_quic_datagram_t), hipMemcpyHostToDevice, s), PTLS_HIP_ENODEV);
-    int e = launch_quic_parse_count(a, walk_grid, stream);
-    /* one scan launch per level; the top level is a single span whose sum is the total */
-    if (e == 0)
-        e = launch_quic_parse_scan(l0, (uint32_t)n, has1 ? l1 : d_total, parse_grid(n1, eng->ncu), stream);
-    if (e == 0 && has1)
-        e = launch_quic_parse_scan(l1, (uint32_t)n1, has2 ? l2 : d_total, parse_grid(n2, eng->ncu), stream);
-    if (e == 0 && has2)
-        e = launch_quic_parse_scan(l2, (uint32_t)n2, d_total, 1, stream);
-    if (e != 0)
-        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-    if (map != nullptr)
-        map->uses.note(stream);
-    sc.mark(1, s);
+    unsigned walk_grid = 1;
     uint32_t total = 0;
-    HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(total), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
-    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    if (int rc = quic_parse_count(who, eng, pr, map, dgrams, n, d_buf, sc.d_dgrams, static_cast<uint32_t *>(sc.d_levels), stream, a,
+                                  &walk_grid, &total, [&](int k) { sc.mark(k, s); }))
+        return rc;
     if (total > cap) {
         *n_pkts = total;
         return fail(PTLS_HIP_EINVAL, "%s: %u entries do not fit the arrays of %zu", who, total, cap);
@@ -301,13 +360,10 @@ extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_
     if (total != 0) {
         HIP_TRY(dev_alloc(eng, &sc.d_pkts, (size_t)total * sizeof(ptls_hip_quic_packet_t)), PTLS_HIP_ENOMEM);
         HIP_TRY(dev_alloc(eng, &sc.d_info, (size_t)total * sizeof(ptls_hip_quic_pktinfo_t)), PTLS_HIP_ENOMEM);
-        a.pkts = static_cast<ptls_hip_quic_packet_t *>(sc.d_pkts);
-        a.info = static_cast<ptls_hip_quic_pktinfo_t *>(sc.d_info);
         sc.mark(2, s);
-        if ((e = launch_quic_parse_write(a, walk_grid, stream)) != 0)
-            return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-        if (map != nullptr)
-            map->uses.note(stream);
+        if (int rc = quic_parse_write(who, map, a, walk_grid, static_cast<ptls_hip_quic_packet_t *>(sc.d_pkts),
+                                      static_cast<ptls_hip_quic_pktinfo_t *>(sc.d_info), stream))
+            return rc;
         sc.mark(3, s);
         HIP_TRY(hipMemcpyAsync(h_pkts, sc.d_pkts, (size_t)total * sizeof(ptls_hip_quic_packet_t), hipMemcpyDeviceToHost, s),
                 PTLS_HIP_ENODEV);

@@ -1,0 +1,425 @@
+/*
+ * quic_rx.cpp -- the receive object (include/ptls_hip.h 2i): parsed entries that stay on the device, and the
+ * open call that selects, packs and plans them there and strings the existing header and record kernels behind: the host
+ * sees the number of entries, five sums per open call, and nothing per packet.  The parse steps are quic_parse.cpp's, the
+ * select rule and the sums' terms quic_rx.h's (shared with quic_rx_kernel.hip), the lane rules planner.cpp's, the record
+ * launch batch.cpp's run_plan.  Where the planner wants the batch kernel (long key runs) the packed descriptors go back to
+ * the host and through ptls_hip_quic_batch_new / ptls_hip_quic_open_batch as they are.
+ */
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+
+#include "host.h"
+
+#define GF128_FN static inline
+#include "quic_rx.h"
+
+namespace {
+
+thread_local bool g_timing = false;
+thread_local float g_select_ms = 0, g_plan_ms = 0;
+
+size_t sort_tiles(size_t m)
+{
+    return (m + QRX_TILE - 1) / QRX_TILE;
+}
+
+} // namespace
+
+struct st_ptls_hip_quic_rx_t {
+    ptls_hip_engine_t *eng = nullptr;
+    size_t max_dgrams = 0, cap = 0;
+    size_t n = 0;          /* entries loaded */
+    bool has_info = false; /* ... with info records */
+    int mode = 0;          /* ptls_hip_quic_rx_set_plan */
+    /* the entries, and the parse call's scratch (max_dgrams datagrams) */
+    ptls_hip_quic_packet_t *d_pkts = nullptr;
+    ptls_hip_quic_pktinfo_t *d_info = nullptr;
+    void *d_dgrams = nullptr;
+    uint32_t *d_parse_levels = nullptr;
+    /* the open call's scratch (cap entries) */
+    uint32_t *d_sel_levels = nullptr; /* the select flags and their scan */
+    ptls_hip_quic_packet_t *d_packed = nullptr;
+    uint32_t *d_keys = nullptr;
+    ptls_hip_record_t *d_recs = nullptr, *d_recs_ord = nullptr;
+    uint32_t *d_order = nullptr, *d_order_tmp = nullptr;
+    uint32_t *d_hist = nullptr; /* the [digit][tile] counts of a radix pass and their scan */
+    uint64_t *d_stats = nullptr;
+    Chunk *d_chunk = nullptr;
+    size_t order_n = 0; /* != 0: d_order holds the last device-made AES plan order of that many packets */
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Uses uses; /* the launches that read or write the arrays above: rx_free waits for them */
+
+    template <class T>
+    int ensure(T **p, size_t bytes)
+    {
+        if (*p != nullptr)
+            return 0;
+        bytes = (bytes + 15) & ~(size_t)15; /* whole 16-byte units: ptls_hip_device_copy can read any array back */
+        if (dev_alloc(eng, reinterpret_cast<void **>(p), bytes) != hipSuccess)
+            return fail(PTLS_HIP_ENOMEM, "quic_rx: cannot allocate %zu bytes of device memory", bytes);
+        return 0;
+    }
+    int ensure_entries()
+    {
+        if (int e = ensure(&d_pkts, cap * sizeof(ptls_hip_quic_packet_t)))
+            return e;
+        return ensure(&d_info, cap * sizeof(ptls_hip_quic_pktinfo_t));
+    }
+    void mark(int k, hipStream_t s)
+    {
+        if (g_timing && (ev[k] != nullptr || hipEventCreate(&ev[k]) == hipSuccess))
+            (void)hipEventRecord(ev[k], s);
+    }
+    float between(int a, int b)
+    {
+        float ms = 0;
+        if (ev[a] == nullptr || ev[b] == nullptr || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess)
+            return 0;
+        return ms;
+    }
+};
+
+extern "C" ptls_hip_quic_rx_t *ptls_hip_quic_rx_new(ptls_hip_engine_t *eng, size_t max_dgrams, size_t cap)
+{
+    if (eng == nullptr || cap < 1 || cap > 0xffffffffu || max_dgrams > 0xffffffffu) {
+        fail(PTLS_HIP_EINVAL, "quic_rx_new: null engine, cap %zu outside 1 .. 2^32 - 1, or max_dgrams %zu above 2^32 - 1", cap,
+             max_dgrams);
+        return nullptr;
+    }
+    auto *rx = new st_ptls_hip_quic_rx_t();
+    rx->eng = eng;
+    rx->max_dgrams = max_dgrams;
+    rx->cap = cap;
+    return rx; /* device memory comes with the first use of each array */
+}
+
+extern "C" void ptls_hip_quic_rx_free(ptls_hip_quic_rx_t *rx)
+{
+    if (rx == nullptr)
+        return;
+    void *const mem[] = {rx->d_pkts,  rx->d_info,     rx->d_dgrams, rx->d_parse_levels, rx->d_sel_levels, rx->d_packed, rx->d_keys,
+                         rx->d_recs,  rx->d_recs_ord, rx->d_order,  rx->d_order_tmp,    rx->d_hist,       rx->d_stats,  rx->d_chunk};
+    bool any = false;
+    for (void *p : mem)
+        any = any || p != nullptr;
+    if (any) {
+        DeviceGuard g(rx->eng->device);
+        rx->uses.wait();
+        for (void *p : mem)
+            dev_free(rx->eng, p);
+        for (hipEvent_t e : rx->ev)
+            if (e != nullptr)
+                (void)hipEventDestroy(e);
+        (void)hipStreamSynchronize(rx->eng->util);
+    }
+    delete rx;
+}
+
+extern "C" int ptls_hip_quic_rx_parse(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
+                                      const ptls_hip_quic_datagram_t *dgrams, size_t n, const void *d_buf, size_t buf_len,
+                                      size_t *n_pkts, void *stream)
+{
+    const char *who = "quic_rx_parse";
+    if (rx == nullptr || pr == nullptr || n_pkts == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null receive object, parameters or n_pkts", who);
+    if (n != 0 && (dgrams == nullptr || d_buf == nullptr))
+        return fail(PTLS_HIP_EINVAL, "%s: null datagram array or buffer", who);
+    if (n > rx->max_dgrams)
+        return fail(PTLS_HIP_EINVAL, "%s: %zu datagrams, the receive object was made for %zu", who, n, rx->max_dgrams);
+    if (int rc = quic_parse_check(who, rx->eng, pr, map, dgrams, n, buf_len))
+        return rc;
+    rx->n = 0;
+    rx->has_info = true;
+    rx->order_n = 0;
+    *n_pkts = 0;
+    if (n == 0)
+        return 0;
+
+    ptls_hip_engine_t *eng = rx->eng;
+    DeviceGuard g(eng->device);
+    if (int e = rx->ensure(&rx->d_dgrams, rx->max_dgrams * sizeof(ptls_hip_quic_datagram_t)))
+        return e;
+    if (int e = rx->ensure(&rx->d_parse_levels, scan_levels(nullptr, rx->max_dgrams).words * sizeof(uint32_t)))
+        return e;
+    if (int e = rx->ensure_entries())
+        return e;
+    QuicParseArgs a{};
+    unsigned walk_grid = 1;
+    uint32_t total = 0;
+    rx->uses.note(stream);
+    if (int rc = quic_parse_count(who, eng, pr, map, dgrams, n, d_buf, rx->d_dgrams, rx->d_parse_levels, stream, a, &walk_grid, &total,
+                                  [](int) {}))
+        return rc;
+    if (total > rx->cap) {
+        *n_pkts = total;
+        return fail(PTLS_HIP_EINVAL, "%s: %u entries do not fit the receive object's %zu", who, total, rx->cap);
+    }
+    if (total != 0) {
+        if (int rc = quic_parse_write(who, map, a, walk_grid, rx->d_pkts, rx->d_info, stream))
+            return rc;
+        rx->uses.note(stream);
+    }
+    rx->n = total;
+    *n_pkts = total;
+    return 0;
+}
+
+extern "C" int ptls_hip_quic_rx_set_packets(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_packet_t *d_pkts,
+                                            const ptls_hip_quic_pktinfo_t *d_info, size_t n, void *stream)
+{
+    const char *who = "quic_rx_set_packets";
+    if (rx == nullptr || (n != 0 && d_pkts == nullptr))
+        return fail(PTLS_HIP_EINVAL, "%s: null receive object or descriptor array", who);
+    if (n > rx->cap)
+        return fail(PTLS_HIP_EINVAL, "%s: %zu descriptors, the receive object holds %zu", who, n, rx->cap);
+    rx->n = 0;
+    rx->has_info = d_info != nullptr;
+    rx->order_n = 0;
+    if (n == 0)
+        return 0;
+    DeviceGuard g(rx->eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int e = rx->ensure_entries())
+        return e;
+    HIP_TRY(hipMemcpyAsync(rx->d_pkts, d_pkts, n * sizeof(ptls_hip_quic_packet_t), hipMemcpyDeviceToDevice, s), PTLS_HIP_ENODEV);
+    if (d_info != nullptr)
+        HIP_TRY(hipMemcpyAsync(rx->d_info, d_info, n * sizeof(ptls_hip_quic_pktinfo_t), hipMemcpyDeviceToDevice, s), PTLS_HIP_ENODEV);
+    rx->uses.note(stream);
+    rx->n = n;
+    return 0;
+}
+
+extern "C" const ptls_hip_quic_packet_t *ptls_hip_quic_rx_packets(ptls_hip_quic_rx_t *rx)
+{
+    return rx != nullptr && rx->n != 0 ? rx->d_pkts : nullptr;
+}
+
+extern "C" const ptls_hip_quic_pktinfo_t *ptls_hip_quic_rx_info(ptls_hip_quic_rx_t *rx)
+{
+    return rx != nullptr && rx->n != 0 && rx->has_info ? rx->d_info : nullptr;
+}
+
+extern "C" size_t ptls_hip_quic_rx_count(ptls_hip_quic_rx_t *rx)
+{
+    return rx != nullptr ? rx->n : 0;
+}
+
+extern "C" int ptls_hip_quic_rx_set_plan(ptls_hip_quic_rx_t *rx, int mode)
+{
+    if (rx == nullptr || mode < 0 || mode > 2)
+        return fail(PTLS_HIP_EINVAL, "quic_rx_set_plan: null receive object, or a mode other than 0 (auto), 1 (device) and 2 (host)");
+    rx->mode = mode;
+    return 0;
+}
+
+extern "C" const uint32_t *ptls_hip_quic_rx_order(ptls_hip_quic_rx_t *rx)
+{
+    return rx != nullptr && rx->order_n != 0 ? rx->d_order : nullptr;
+}
+
+extern "C" void ptls_hip_quic_rx_timing(int enable, float *select_ms, float *plan_ms)
+{
+    g_timing = enable != 0;
+    if (select_ms != nullptr)
+        *select_ms = g_select_ms;
+    if (plan_ms != nullptr)
+        *plan_ms = g_plan_ms;
+}
+
+/* one stable radix pass over m positions: counts, their scan, placement */
+static int radix_pass(ptls_hip_quic_rx_t *rx, const uint32_t *src, uint32_t m, uint32_t shift, uint32_t *dst, void *stream)
+{
+    const ScanLevels H = scan_levels(rx->d_hist, QRX_DIGITS * sort_tiles(m));
+    int e = launch_quic_rx_hist(rx->d_keys, src, m, shift, H.l0, stream);
+    if (e == 0)
+        e = launch_scan_levels(H, rx->eng->ncu, stream);
+    if (e == 0)
+        e = launch_quic_rx_scatter(rx->d_keys, src, m, shift, H.l0, H.has1 ? H.l1 : nullptr, H.has2 ? H.l2 : nullptr, dst, stream);
+    return e;
+}
+
+/* the packed descriptors back to the host and through the existing calls, planned there */
+static int open_on_host(ptls_hip_quic_rx_t *rx, size_t m, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, void *d_buf, void *d_out,
+                        uint64_t *d_result, uint64_t *d_pn_out, ptls_hip_quic_rx_report_t *report, void *stream)
+{
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::vector<ptls_hip_quic_packet_t> h(m);
+    HIP_TRY(hipMemcpyAsync(h.data(), rx->d_packed, m * sizeof(ptls_hip_quic_packet_t), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
+    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    ptls_hip_quic_batch_t *q = ptls_hip_quic_batch_new(rx->eng, h.data(), m, 1, stream);
+    if (q == nullptr)
+        return PTLS_HIP_EINVAL; /* (the message is batch_new's) */
+    int lanes = 0, chacha_lanes = 0;
+    quic_batch_lanes(q, &lanes, &chacha_lanes);
+    report->lanes = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305 ? chacha_lanes : lanes;
+    const int rc = ptls_hip_quic_open_batch(q, ks, hp_ks, d_buf, d_out, d_result, d_pn_out, stream);
+    ptls_hip_quic_batch_free(q); /* waits for the launches */
+    return rc;
+}
+
+extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, uint32_t type_mask,
+                                     void *d_buf, size_t buf_len, void *d_out, size_t out_len, uint32_t *d_sel, uint64_t *d_result,
+                                     uint64_t *d_pn_out, ptls_hip_quic_rx_report_t *report, void *stream)
+{
+    const char *who = "quic_rx_open";
+    if (rx == nullptr || ks == nullptr || hp_ks == nullptr || report == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null receive object, keyset or report", who);
+    if (ks->eng != rx->eng || hp_ks->eng != rx->eng)
+        return fail(PTLS_HIP_EINVAL, "%s: receive object and keysets must belong to the same engine", who);
+    if (hp_ks->algo != ks->algo || hp_ks->key_size != ks->key_size)
+        return fail(PTLS_HIP_EINVAL, "%s: the header-protection keyset must be of the AEAD keyset's algorithm and key size", who);
+    report->n_selected = 0;
+    report->planned_on_device = 0;
+    report->lanes = 0;
+    if (rx->n == 0)
+        return 0;
+    if (d_buf == nullptr || d_out == nullptr || d_sel == nullptr || d_result == nullptr || d_pn_out == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null buffer", who);
+    {
+        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
+        if (buf_len != 0 && out_len != 0 && b < o + out_len && o < b + buf_len)
+            return fail(PTLS_HIP_EINVAL, "%s: the output buffer overlaps the packet buffer", who);
+    }
+
+    ptls_hip_engine_t *eng = rx->eng;
+    DeviceGuard g(eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const size_t cap = rx->cap;
+    int e = rx->ensure(&rx->d_sel_levels, scan_levels(nullptr, cap).words * sizeof(uint32_t));
+    if (e == 0)
+        e = rx->ensure(&rx->d_packed, cap * sizeof(ptls_hip_quic_packet_t));
+    if (e == 0)
+        e = rx->ensure(&rx->d_keys, cap * sizeof(uint32_t));
+    if (e == 0)
+        e = rx->ensure(&rx->d_recs, cap * sizeof(ptls_hip_record_t));
+    if (e == 0)
+        e = rx->ensure(&rx->d_stats, QRX_NSTATS * sizeof(uint64_t));
+    if (e == 0)
+        e = rx->ensure(&rx->d_chunk, sizeof(Chunk));
+    if (e != 0)
+        return e;
+    rx->order_n = 0;
+
+    /* select, scan, compact, stats: one readback of QRX_NSTATS sums is all the host learns of the packets */
+    const ScanLevels L = scan_levels(rx->d_sel_levels, rx->n);
+    QuicRxLimits lim{};
+    lim.buf_len = buf_len;
+    lim.out_len = out_len;
+    lim.nslots = ks->nslots;
+    lim.hp_nslots = hp_ks->nslots;
+    lim.type_mask = type_mask;
+    lim.has_info = rx->has_info ? 1u : 0u;
+    QuicRxArgs a{};
+    a.pkts = rx->d_pkts;
+    a.info = rx->has_info ? rx->d_info : nullptr;
+    a.n = (uint32_t)rx->n;
+    a.l0 = L.l0;
+    a.l1 = L.has1 ? L.l1 : nullptr;
+    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.total = L.total;
+    a.sel = d_sel;
+    a.packed = rx->d_packed;
+    a.keys = rx->d_keys;
+    a.stats = rx->d_stats;
+    a.chunk = rx->d_chunk;
+    const unsigned grid = quic_scan_grid((rx->n + 255) / 256, eng->ncu);
+    rx->mark(0, s);
+    e = launch_quic_rx_select(a, lim, grid, stream);
+    if (e == 0)
+        e = launch_scan_levels(L, eng->ncu, stream);
+    if (e == 0)
+        e = launch_quic_rx_compact(a, lim, grid, stream);
+    if (e == 0)
+        e = launch_quic_rx_stats(a, grid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    rx->uses.note(stream);
+    rx->mark(1, s);
+    uint64_t st[QRX_NSTATS] = {};
+    HIP_TRY(hipMemcpyAsync(st, rx->d_stats, sizeof(st), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
+    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    if (g_timing)
+        g_select_ms = rx->between(0, 1), g_plan_ms = 0;
+    const size_t m = (size_t)st[QRX_STAT_COUNT];
+    report->n_selected = m;
+    if (m == 0)
+        return 0;
+
+    /* the lanes, by the planner's rules from the sums (integers below 2^53: exact in a double) */
+    const bool chacha = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
+    const int lanes = choose_lanes_from((double)st[QRX_STAT_GHASH], m, (size_t)st[QRX_STAT_RUNS] + 1, (unsigned)eng->ncu);
+    const int chacha_lanes = choose_chacha_lanes_from((double)st[QRX_STAT_BLOCKS64], m, (unsigned)eng->ncu);
+    const bool on_device = rx->mode == 1 || (rx->mode == 0 && (chacha || lanes == SPARSE_LANES));
+    if (!on_device)
+        return open_on_host(rx, m, ks, hp_ks, d_buf, d_out, d_result, d_pn_out, report, stream);
+
+    LaunchPlan p{};
+    p.eng = eng;
+    p.n = m;
+    p.d_recs = rx->d_recs;
+    p.wg = WG_ALT;
+    p.lanes = SPARSE_LANES;
+    p.chacha_lanes = chacha_lanes;
+    p.all_aligned = false; /* packets lie at any byte offset; the header kernel writes the real in_off */
+    p.ncus = (unsigned)eng->ncu;
+    if (!chacha) {
+        /* the sparse kernel's plan: a stable order by decreasing 16-byte block count, two radix digits of the 12-bit key */
+        e = rx->ensure(&rx->d_recs_ord, cap * sizeof(ptls_hip_record_t));
+        const bool fresh = rx->d_order == nullptr;
+        if (e == 0)
+            e = rx->ensure(&rx->d_order, cap * sizeof(uint32_t));
+        if (e == 0)
+            e = rx->ensure(&rx->d_order_tmp, cap * sizeof(uint32_t));
+        if (e == 0 && fresh) { /* once: every word the header kernel could ever read as a position is a valid one */
+            HIP_TRY(hipMemsetAsync(rx->d_order, 0, cap * sizeof(uint32_t), s), PTLS_HIP_ENODEV);
+            HIP_TRY(hipMemsetAsync(rx->d_order_tmp, 0, cap * sizeof(uint32_t), s), PTLS_HIP_ENODEV);
+        }
+        if (e == 0)
+            e = rx->ensure(&rx->d_hist, scan_levels(nullptr, QRX_DIGITS * sort_tiles(cap)).words * sizeof(uint32_t));
+        if (e != 0)
+            return e;
+        rx->mark(2, s);
+        e = radix_pass(rx, nullptr, (uint32_t)m, 0, rx->d_order_tmp, stream);
+        if (e == 0)
+            e = radix_pass(rx, rx->d_order_tmp, (uint32_t)m, QRX_DIGIT_BITS, rx->d_order, stream);
+        if (e != 0)
+            return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+        rx->mark(3, s);
+        p.d_recs_ord = rx->d_recs_ord;
+        p.d_order = rx->d_order;
+        p.d_chunks = rx->d_chunk;
+        p.nchunks = 1;
+    }
+    QuicArgs q{};
+    q.pkts = rx->d_packed;
+    q.n = (uint32_t)m;
+    q.order = chacha ? nullptr : rx->d_order;
+    q.recs = rx->d_recs;
+    q.recs_ord = chacha ? nullptr : rx->d_recs_ord;
+    q.pkt = static_cast<uint8_t *>(d_buf);
+    q.pn_out = d_pn_out;
+    q.hp_slots = hp_ks->d_slots;
+    q.hp_chacha = hp_ks->d_chacha;
+    q.t0 = eng->d_t0;
+    const size_t wgs = (m + 255) / 256; /* (quic.cpp quic_grid) */
+    const unsigned hgrid = (unsigned)(chacha ? wgs : std::min<size_t>(wgs, (size_t)eng->ncu * 4));
+    e = launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, q, hgrid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    keyset_note_use(hp_ks, stream);
+    rx->uses.note(stream);
+    if (int rc = run_plan(p, ks, d_buf, d_buf, d_out, d_result, stream, true))
+        return rc;
+    rx->uses.note(stream);
+    if (!chacha)
+        rx->order_n = m;
+    if (g_timing && !chacha && rx->ev[3] != nullptr) { /* (a diagnostic: it waits for the sort, not for the open kernel) */
+        (void)hipEventSynchronize(rx->ev[3]);
+        g_plan_ms = rx->between(2, 3);
+    }
+    report->planned_on_device = 1;
+    report->lanes = chacha ? chacha_lanes : SPARSE_LANES;
+    return 0;
+}

@@ -113,6 +113,17 @@ SIGNATURES = {
     "ptls_hip_quic_cidmap_remove": (_i, [_vp, _sz, _vp, _vp, _vp]),
     "ptls_hip_quic_parse_datagrams": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _sz, ctypes.POINTER(_sz), _vp]),
     "ptls_hip_quic_parse_timing": (None, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "ptls_hip_quic_rx_new": (_vp, [_vp, _sz, _sz]),
+    "ptls_hip_quic_rx_free": (None, [_vp]),
+    "ptls_hip_quic_rx_parse": (_i, [_vp, _vp, _vp, _vp, _sz, _vp, _sz, ctypes.POINTER(_sz), _vp]),
+    "ptls_hip_quic_rx_set_packets": (_i, [_vp, _vp, _vp, _sz, _vp]),
+    "ptls_hip_quic_rx_packets": (_vp, [_vp]),
+    "ptls_hip_quic_rx_info": (_vp, [_vp]),
+    "ptls_hip_quic_rx_count": (_sz, [_vp]),
+    "ptls_hip_quic_rx_open": (_i, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_quic_rx_set_plan": (_i, [_vp, _i]),
+    "ptls_hip_quic_rx_order": (_vp, [_vp]),
+    "ptls_hip_quic_rx_timing": (None, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -543,6 +554,90 @@ def quic_parse_datagrams(engine, dgrams, d_buf, buf_len, cidmap=None, short_cid_
                                                info.ctypes.data, cap, ctypes.byref(n_pkts), _stream(stream)),
            "quic_parse_datagrams")
     return pkts[:n_pkts.value], info[:n_pkts.value]
+
+
+QUIC_RX_PLAN_AUTO, QUIC_RX_PLAN_DEVICE, QUIC_RX_PLAN_HOST = 0, 1, 2
+QUIC_ALL_TYPES = 0xFF
+
+
+class QuicRxReport(ctypes.Structure):
+    """ptls_hip_quic_rx_report_t"""
+    _fields_ = [("n_selected", ctypes.c_uint64), ("planned_on_device", ctypes.c_int32), ("lanes", ctypes.c_int32)]
+
+
+class QuicRx:
+    """the receive object (ptls_hip_quic_rx_*): parsed entries stay on the device; open() selects, packs, plans and opens
+    them there.  Calls on one QuicRx must be ordered (same stream)."""
+
+    def __init__(self, engine, max_dgrams, cap):
+        self.engine, self.max_dgrams, self.cap = engine, max_dgrams, cap
+        self.ptr = lib().ptls_hip_quic_rx_new(engine.ptr, max_dgrams, cap)
+        if not self.ptr:
+            raise HipError(f"ptls_hip_quic_rx_new: {last_error()}")
+
+    def __len__(self):
+        return lib().ptls_hip_quic_rx_count(self.ptr)
+
+    def parse(self, dgrams, d_buf, buf_len, cidmap=None, short_cid_len=0, max_per_dgram=16, require_fixed_bit=1, expected_pn=None,
+              expected_count=None, stream=None):
+        """ptls_hip_quic_rx_parse: as quic_parse_datagrams, the entries stay on the device; returns their number"""
+        dgrams = np.ascontiguousarray(dgrams, dtype=QUIC_DATAGRAM_DTYPE)
+        if expected_count is None:
+            expected_count = expected_pn.numel() if expected_pn is not None else 0
+        params = QuicParseParams(short_cid_len, max_per_dgram, require_fixed_bit, 0, _ptr(expected_pn), expected_count)
+        n_pkts = ctypes.c_size_t(0)
+        _check(lib().ptls_hip_quic_rx_parse(self.ptr, ctypes.addressof(params), cidmap.ptr if cidmap is not None else None,
+                                            dgrams.ctypes.data, len(dgrams), _ptr(d_buf), buf_len, ctypes.byref(n_pkts),
+                                            _stream(stream)), "quic_rx_parse")
+        return n_pkts.value
+
+    def set_packets(self, d_pkts, d_info, n, stream=None):
+        """n descriptors (and info records, or None) the caller has in device memory"""
+        _check(lib().ptls_hip_quic_rx_set_packets(self.ptr, _ptr(d_pkts), _ptr(d_info), n, _stream(stream)), "quic_rx_set_packets")
+
+    def _read(self, ptr, dtype, n):
+        """n items at the object's device pointer `ptr` as a numpy array (its arrays are whole 16-byte units, so
+        ptls_hip_device_copy can bring them into a tensor)"""
+        import torch
+        if n == 0:
+            return np.zeros(0, dtype=dtype)
+        nbytes = (n * dtype.itemsize + 15) & ~15
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.engine.device}")
+        self.engine.copy(dev, ptr, nbytes)
+        return dev.cpu().numpy()[:n * dtype.itemsize].view(dtype).copy()
+
+    def packets(self):
+        """the loaded descriptors, read back (tests)"""
+        n = len(self)
+        return self._read(lib().ptls_hip_quic_rx_packets(self.ptr), QUIC_PACKET_DTYPE, n)
+
+    def info(self):
+        """the loaded info records, read back, or None when there are none (tests)"""
+        p = lib().ptls_hip_quic_rx_info(self.ptr)
+        return self._read(p, QUIC_PKTINFO_DTYPE, len(self)) if p else None
+
+    def order(self, n_selected):
+        """the last device-made AES plan order, read back, or None"""
+        p = lib().ptls_hip_quic_rx_order(self.ptr)
+        return self._read(p, np.dtype("<u4"), n_selected) if p else None
+
+    def set_plan(self, mode):
+        _check(lib().ptls_hip_quic_rx_set_plan(self.ptr, mode), "quic_rx_set_plan")
+
+    def open(self, keyset, hp_keyset, d_buf, buf_len, d_out, out_len, d_sel, d_result, d_pn_out, type_mask=QUIC_ALL_TYPES,
+             stream=None):
+        """selects the openable entries (of the types in type_mask), d_sel[j] = the entry of the j-th selected packet, opens
+        them into d_out + data_off; returns the QuicRxReport (n_selected, planned_on_device, lanes)"""
+        rep = QuicRxReport()
+        _check(lib().ptls_hip_quic_rx_open(self.ptr, keyset.ptr, hp_keyset.ptr, type_mask, _ptr(d_buf), buf_len, _ptr(d_out), out_len,
+                                           _ptr(d_sel), _ptr(d_result), _ptr(d_pn_out), ctypes.addressof(rep), _stream(stream)),
+               "quic_rx_open")
+        return rep
+
+    def close(self):
+        if self.ptr:
+            lib().ptls_hip_quic_rx_free(self.ptr)
+            self.ptr = None
 
 
 def partition_bytes(recs, parts):

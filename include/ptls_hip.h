@@ -516,7 +516,7 @@ ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *batch);
  * packets, the long-header fields up to pn_offset and pkt_len, and the key slot from the Destination Connection ID.
  * Out of scope: the node API (2d); handling Retry and Version Negotiation packets (they carry no packet protection; 2h
  * reports them and the host answers); choosing the key by key phase on the device (the AES planner needs every packet's
- * key slot on the host). */
+ * key slot on the host; 2i plans on the device where the kernel's plan does not depend on the keys). */
 int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
                              void *pkt, void *stream);
 int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, void *pkt, void *out,
@@ -612,7 +612,7 @@ int ptls_hip_pipeline_quic_open(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, p
 /* The receive side in front of 2e: UDP datagrams in device memory go in, the packet descriptors of 2e come out, ready for
  * ptls_hip_quic_batch_new(..., open = 1), each with an info record.  The host still plans the open batch (40 + 32 bytes per
  * packet come back instead of the packets) and decides what to do with Retry, Version Negotiation and unknown-version
- * packets. */
+ * packets.  (The receive object of 2i keeps the entries on the device and opens them from there.) */
 
 #define PTLS_HIP_QUIC_TYPE_INITIAL 0u
 #define PTLS_HIP_QUIC_TYPE_ZERO_RTT 1u
@@ -726,6 +726,79 @@ int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *engine, const ptls_hip_quic
  * kernels_ms / d2h_ms (either may be NULL) receive the last such call's kernel time (upload of the datagram array, count,
  * scan and write passes) and the time of the copies of the entries back to the host. */
 void ptls_hip_quic_parse_timing(int enable, float *kernels_ms, float *d2h_ms);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2i. the receive object: parsed entries stay on the device and are selected, packed, planned   *
+ *     and opened from there                                                                     *
+ * ------------------------------------------------------------------------------------------ */
+
+/* 2h followed by 2e costs a copy of 72 bytes per packet to the host, the host's planning of the open batch and the upload of
+ * its plan.  A receive object keeps the entries of a parse call in device memory and opens them with one call: which entries
+ * can be opened is decided on the device, they are packed in entry order, the planner's sums are taken there, and for the
+ * ChaCha20-Poly1305 kernel (which needs no plan) and the wave-per-record AES kernel (whose plan is a sort by length) the
+ * existing header and record kernels follow at once.  The host reads five 64-bit sums per open call.  Where the planner wants
+ * the AES batch kernel (key runs of 20 records and more on average), the packed descriptors (40 bytes each) go back to the
+ * host and through ptls_hip_quic_batch_new / ptls_hip_quic_open_batch unchanged (report.planned_on_device = 0).
+ *
+ * rx_new: room for max_dgrams datagrams per parse call and cap entries; device memory is allocated with the first use of each
+ *   array and kept, so the calls allocate nothing per call.  NULL for a null engine, cap outside 1 .. 2^32 - 1 or max_dgrams
+ *   above 2^32 - 1.  rx_free waits for the launches that used the object.
+ * rx_parse: the walk, the rules and the refusals of ptls_hip_quic_parse_datagrams, byte for byte, into the object's device
+ *   arrays; the host learns *n_pkts only.  Also PTLS_HIP_EINVAL: n above max_dgrams; more entries than cap (after the
+ *   counting pass, *n_pkts = the number needed, no entry loaded).  Synchronises `stream` once (the count).
+ * rx_set_packets: instead, n descriptors, and optionally their info records, that the caller already has in DEVICE memory
+ *   (copied on `stream`); PTLS_HIP_EINVAL for n above cap.  Either call replaces the entries loaded before; n == 0 unloads.
+ * rx_packets / rx_info / rx_count: the loaded entries (device pointers, NULL when none / no info records) and their number.
+ *
+ * rx_open selects entry k if and only if
+ *   pn_offset != 0, pn_offset + 20 <= pkt_len <= 65535, pkt_off + pkt_len <= buf_len,
+ *   data_off + (pkt_len - pn_offset - 17) <= out_len   (the plaintext area at its pn_len = 1 size),
+ *   key < the slots of ks and hp_key < the slots of hp_ks   (PTLS_HIP_QUIC_NO_CONN never is),
+ *   and, where info records are loaded, (type_mask >> info[k].type) & 1.
+ * These are the per-packet refusals of 2e's calls, applied per packet on the device: an unselected entry is skipped, not an
+ * error.  Selected entries keep their order: d_sel[j] = the entry index of the j-th selected packet, d_result[j] and
+ * d_pn_out[j] as ptls_hip_quic_open_batch defines them for it; exactly report->n_selected elements of each are written.  In
+ * d_buf only the 1 + pn_len header bytes of selected packets are written (none with PTLS_HIP_QUIC_UNPROTECTED in the
+ * descriptor's flags), in d_out exactly their plaintext bytes, on failure too.  One parse may be followed by several opens
+ * with other masks and keysets (Handshake, then 1-RTT), each with its own output arrays.  All five arrays are device memory
+ * (cap elements are always enough).  report->lanes: the lanes per record of the launch (64: the wave-per-record AES kernel).
+ * PTLS_HIP_EINVAL, nothing launched: a null object, keyset or report; keysets of another engine than the object's, or of
+ * different algorithms or key sizes; with entries loaded, a null buffer or [d_buf, buf_len) overlapping [d_out, out_len).
+ * No entries loaded: 0 with n_selected = 0.
+ * Ordering: calls on one receive object must be ordered by the caller (same stream, or own synchronisation), as for a QUIC
+ * batch.  rx_open synchronises `stream` once, to read the sums, and returns with the header and record kernels in flight;
+ * on the host-planned path it returns when they are done.
+ *
+ * rx_set_plan: 0 = as above; 1 = the device plan whatever the key runs (AES: the wave-per-record kernel); 2 = the host plan
+ *   for every cipher.  For tests and A/B measurements: the outputs are the same.  PTLS_HIP_EINVAL for another value.
+ * rx_order: device array of n_selected positions, the plan order of the last open call if it planned AES on the device (a
+ *   stable order of the selected packets by decreasing (pkt_len - pn_offset - 17) >> 4), else NULL.
+ * rx_timing: diagnostic (tools/bench_quic_rx.py), as ptls_hip_quic_parse_timing: HIP-event times of the last rx_open's
+ *   select / scan / compact / sums launches and of its sort launches.
+ * Out of scope: key-run chunks for the AES batch kernel made on the device; grouping interleaved packets by key; the key
+ * phase; key slots for Initial packets of unknown connections; the host pipelines (2g) and the node API (2d). */
+typedef struct st_ptls_hip_quic_rx_t ptls_hip_quic_rx_t;
+typedef struct st_ptls_hip_quic_rx_report_t {
+    uint64_t n_selected;
+    int32_t planned_on_device;
+    int32_t lanes;
+} ptls_hip_quic_rx_report_t;
+ptls_hip_quic_rx_t *ptls_hip_quic_rx_new(ptls_hip_engine_t *engine, size_t max_dgrams, size_t cap);
+void ptls_hip_quic_rx_free(ptls_hip_quic_rx_t *rx);
+int ptls_hip_quic_rx_parse(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_parse_params_t *params, ptls_hip_quic_cidmap_t *map,
+                           const ptls_hip_quic_datagram_t *dgrams, size_t n, const void *d_buf, size_t buf_len, size_t *n_pkts,
+                           void *stream);
+int ptls_hip_quic_rx_set_packets(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_packet_t *d_pkts,
+                                 const ptls_hip_quic_pktinfo_t *d_info, size_t n, void *stream);
+const ptls_hip_quic_packet_t *ptls_hip_quic_rx_packets(ptls_hip_quic_rx_t *rx);
+const ptls_hip_quic_pktinfo_t *ptls_hip_quic_rx_info(ptls_hip_quic_rx_t *rx);
+size_t ptls_hip_quic_rx_count(ptls_hip_quic_rx_t *rx);
+int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, uint32_t type_mask, void *d_buf,
+                          size_t buf_len, void *d_out, size_t out_len, uint32_t *d_sel, uint64_t *d_result, uint64_t *d_pn_out,
+                          ptls_hip_quic_rx_report_t *report, void *stream);
+int ptls_hip_quic_rx_set_plan(ptls_hip_quic_rx_t *rx, int mode);
+const uint32_t *ptls_hip_quic_rx_order(ptls_hip_quic_rx_t *rx);
+void ptls_hip_quic_rx_timing(int enable, float *select_ms, float *plan_ms);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
