@@ -203,6 +203,16 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
 int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result, void *stream,
              bool open, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, void *mask)
 {
+    if (int e = launch_plan(p, ks, in, aad, out, result, stream, open, hp_ks, supp, mask))
+        return e;
+    keyset_note_use(ks, stream);
+    keyset_note_use(hp_ks, stream);
+    return 0;
+}
+
+int launch_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result,
+                void *stream, bool open, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, void *mask)
+{
     DeviceGuard g(p.eng->device);
     const uint8_t *in8 = static_cast<const uint8_t *>(in), *aad8 = static_cast<const uint8_t *>(aad != nullptr ? aad : in);
     const bool aligned = p.all_aligned && ((reinterpret_cast<uintptr_t>(in8) | reinterpret_cast<uintptr_t>(aad8) |
@@ -221,7 +231,8 @@ int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const v
         a.hp_slots = hp_ks != nullptr ? hp_ks->d_chacha : nullptr;
         a.hp_nslots = hp_ks != nullptr ? (uint32_t)hp_ks->nslots : 0;
         a.mask = static_cast<uint8_t *>(mask);
-        e = launch_chacha_batch(p.chacha_lanes, open, stream, a, aligned);
+        e = p.chacha_runs ? launch_chacha_runs(p.chacha_lanes, open, stream, a, aligned)
+                          : launch_chacha_batch(p.chacha_lanes, open, stream, a, aligned);
     } else {
         KernelArgs a{};
         a.recs = p.d_recs;
@@ -246,8 +257,6 @@ int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const v
     }
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    keyset_note_use(ks, stream);
-    keyset_note_use(hp_ks, stream);
     return 0;
 }
 

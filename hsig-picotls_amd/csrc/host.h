@@ -7,8 +7,10 @@
  *                      secrets and Initial keys (kernels: keyschedule.hip, quic_keys.hip; the QUIC arithmetic shared with
  *                      the CPU check: quic_keys.h)
  *   planner.cpp        the launch planner: lanes per record, chunks, grid
- *   batch.cpp          batches and the device-resident seal / open / header-protection calls
- *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls
+ *   batch.cpp          batches and the device-resident seal / open / header-protection calls; the one record launch of a
+ *                      plan (launch_plan, run_plan), which the pipelines and the receive object share
+ *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls, and the two
+ *                      header steps every QUIC path launches through (quic_unprotect, quic_protect)
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
  *   quic_parse.cpp     QUIC datagrams parsed on the device into the packet descriptors of quic.cpp, and the connection-ID map
  *                      (kernels: quic_parse_kernel.hip; the walk and the map arithmetic shared with the CPU check: quic_parse.h)
@@ -17,8 +19,9 @@
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
  *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)
- *   pipeline.cpp       host-resident records and QUIC packets: the mapped and copy transports over one slice launcher
- *                      (launch_slice), for AES-GCM or ChaCha20-Poly1305 keysets (the latter: chacha_kernel.hip,
+ *   pipeline.cpp       host-resident records and QUIC packets: the mapped and copy transports over one slice loop
+ *                      (run_slices) and one slice launcher (launch_slice: it plans, uploads and calls batch.cpp's
+ *                      launch_plan), for AES-GCM or ChaCha20-Poly1305 keysets (the latter: chacha_kernel.hip,
  *                      chacha_runs_kernel.hip; the copy transport's QUIC header return: quic_slice_kernel.hip)
  *   node.cpp           one batch over several devices, NUMA placement
  *   plugin_worker.cpp  the picotls plugin's runtime: the resident worker dispatch and pooled resources
@@ -237,6 +240,8 @@ int plan_wg(const std::vector<Chunk> &ch, int lanes);
 void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned ncu, std::vector<Chunk> &ch,
                   std::vector<uint32_t> &order, bool &all_aligned);
 bool identity_order(const std::vector<uint32_t> &order, size_t n);
+/* every descriptor's in / out / aad offset is a multiple of 16: what build_chunks reports as all_aligned */
+bool offsets_aligned(const ptls_hip_record_t *recs, size_t n);
 
 /* ---- slice_plan.cpp: what the copy transport places where, per slice (arithmetic on descriptors, no HIP call) ---- */
 /* what a pipeline slice runs: plain seal / open (AAD in its own buffer), or the TLS 1.3 record layer
@@ -332,24 +337,32 @@ int run_batch(ptls_hip_batch_t *b, ptls_hip_keyset_t *ks, const void *in, const 
               void *stream, bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr,
               void *mask = nullptr, int algo = 0);
 
-/* what one seal / open launch reads of a plan, wherever the plan was made: a batch's (run_batch), or the device-made one of
- * the QUIC receive step (quic_rx.cpp), which has no ptls_hip_batch_t and no host mirror of its descriptors */
+/* what one seal / open launch reads of a plan, wherever the plan was made: a batch's (run_batch), the device-made one of
+ * the QUIC receive step (quic_rx.cpp), which has no ptls_hip_batch_t and no host mirror of its descriptors, or a pipeline
+ * slice's in its slot (pipeline.cpp).  (The descriptors are not const: the QUIC open header step, quic_unprotect, rewrites
+ * them on the stream before the launch.) */
 struct LaunchPlan {
     ptls_hip_engine_t *eng;
     size_t n;
-    const ptls_hip_record_t *d_recs;
-    const ptls_hip_record_t *d_recs_ord; /* plan order, or nullptr: d_recs serves as both and d_order is nullptr */
+    ptls_hip_record_t *d_recs;
+    ptls_hip_record_t *d_recs_ord; /* plan order, or nullptr: d_recs serves as both and d_order is nullptr */
     const uint32_t *d_order;
-    const Chunk *d_chunks;
+    const Chunk *d_chunks; /* AES-GCM only, as nchunks, lanes and wg: the ChaCha kernels take the records in descriptor order */
     uint32_t nchunks;
     int lanes, wg, chacha_lanes;
-    bool all_aligned;
+    bool chacha_runs; /* ChaCha: chacha_runs_kernel.hip (launch_chacha_runs), not chacha_kernel.hip's (launch_chacha_batch) */
+    bool all_aligned; /* offsets_aligned of the descriptors; the launch adds the alignment of the bases it is given */
     unsigned ncus;   /* CUs the launch is sized for (batch_cus) */
     uint64_t *d_clk; /* diagnostic clock stamps, or nullptr */
     size_t clk_bytes;
 };
-/* the launch of run_batch behind its refusals: n != 0, non-null buffers, every key slot inside the keyset.  Notes the use
- * of the keysets; the caller notes the use of whatever owns the plan */
+/* the launch of run_batch behind its refusals: n != 0, non-null buffers, every key slot inside the keyset: the kernel of
+ * the keyset's algorithm with the plan's arrays, aligned when the plan is and in / aad / out are (aad == nullptr: none, the
+ * kernels get `in`).  It notes no use: for a caller that waits for the stream itself (the pipelines) */
+int launch_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result,
+                void *stream, bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr,
+                void *mask = nullptr);
+/* launch_plan, then the use of the keysets is noted; the caller notes the use of whatever owns the plan */
 int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const void *aad, void *out, uint64_t *result, void *stream,
              bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr, void *mask = nullptr);
 
@@ -378,6 +391,15 @@ int quic_parse_write(const char *who, ptls_hip_quic_cidmap_t *map, QuicParseArgs
 /* ---- quic.cpp ---- */
 /* the lanes the inner batch of a QUIC batch was planned with (the AES batch kernel's, the ChaCha kernel's) */
 void quic_batch_lanes(ptls_hip_quic_batch_t *q, int *lanes, int *chacha_lanes);
+/* The header steps of n packets d_pkts in the buffer pkt, on `stream`; both return 0 or the launch's hipError_t and note no
+ * use.  Open (quic_unprotect_kernel, before the record open): hp_ks's algorithm and key size give the kernel; it writes
+ * the packet numbers to pn_out and the real descriptors to the record plan's d_recs, and to d_recs_ord through d_order
+ * where the plan has an order.  The three are taken as they are (null order: plan position = index; pn_out and d_recs are
+ * indexed by packet).  Seal (quic_protect_kernel, behind the record seal that wrote the 16-byte masks d_mask). */
+int quic_unprotect(ptls_hip_engine_t *eng, const ptls_hip_keyset_t *hp_ks, const ptls_hip_quic_packet_t *d_pkts, size_t n,
+                   ptls_hip_record_t *d_recs, ptls_hip_record_t *d_recs_ord, const uint32_t *d_order, void *pkt, uint64_t *pn_out,
+                   void *stream);
+int quic_protect(const ptls_hip_quic_packet_t *d_pkts, size_t n, void *pkt, const uint8_t *d_mask, void *stream);
 
 /* ---- plugin_worker.cpp ---- */
 /* ptls_hip_keyset_free of a plugin context's pooled slot */

@@ -60,7 +60,7 @@ struct st_ptls_hip_pipeline_t {
     int chacha_lanes;   /* ChaCha pipelines: 0 = from the slice's records, or the forced width (1, 4, 16, 64) */
     int chacha_layout;  /* ... and PTLS_HIP_CHACHA_LAYOUT_* */
     PipeSlot slot[NSLOT];
-    /* scratch of launch_slice: the slice's launch plan */
+    /* scratch of launch_slice alone: the chunks and the order of the AES-GCM slice it is planning */
     std::vector<Chunk> ch;
     std::vector<uint32_t> order;
 };
@@ -239,6 +239,13 @@ static void *mapped_span(const void *h, uint64_t need, bool *partial)
     return d;
 }
 
+/* the refusal of a call that mapped_span found such a buffer in */
+static int refuse_partial()
+{
+    return fail(PTLS_HIP_EINVAL, "pipeline: a host buffer is pinned or registered only in part (its mapping ends before "
+                                 "the last byte the records touch): neither transport can use it");
+}
+
 /* lanes per record when the kernel reads and writes host memory: the launch is PCIe-bound, not LDS-bound, and wider
  * lane groups turn each load / store instruction into longer contiguous runs per record, i.e. fewer, larger PCIe
  * requests.  Measured (tools/hostmem_probe.py, seal+open GiB/s at 4 / 8 / 16 / 32 lanes): 1350-B records 31.7 /
@@ -349,44 +356,58 @@ static void drain_slots(ptls_hip_pipeline_t *p)
     }
 }
 
-/* One slice on slot s, the same for both transports, once its slice-local descriptors sit in s.h_recs (and s.h_supp):
- * the launch plan, the descriptor uploads, the TLS 1.3 header kernel, the record kernel and the inner-plaintext kernel,
- * in that order on s.stream.  in / aad / out / result / mask are device addresses: of the caller's mapped buffers, or of
- * the slot's staging.  `payload` queues what the transport itself uploads for the slice (copy: the records' bytes and
- * the gaps) between the descriptor uploads and the kernels, where the copy transport always queued it. */
-template <class Payload>
-static int launch_chacha_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, ChaChaPlan plan,
-                               const ModeInfo &m, const uint8_t *in, const uint8_t *aad, uint8_t *out, uint64_t *result,
-                               ptls_hip_keyset_t *hp_ks, bool have_supp, uint8_t *mask, Payload payload);
-
-/* (lanes: of the AES-GCM kernels; a ChaCha pipeline's slices take theirs from chacha_plan) */
-template <class Payload>
-static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, int lanes, const ModeInfo &m,
-                        const uint8_t *in, const uint8_t *aad, uint8_t *out, uint64_t *result, ptls_hip_keyset_t *hp_ks,
-                        bool have_supp, uint8_t *mask, bool mapped, Payload payload)
+/* One slice on slot s, the same for both transports and both algorithms, once its slice-local descriptors sit in s.h_recs
+ * (and s.h_supp): the launch plan, the descriptor uploads, `hook`, the TLS 1.3 header kernel, the record kernel (batch.cpp's
+ * launch_plan: the pipeline waits for every slice itself and notes no keyset use) and the inner-plaintext kernel, in that
+ * order on s.stream.  in / aad / out / result / mask are device addresses: of the caller's mapped buffers, or of the slot's
+ * staging.  `hook(plan)` queues what the transport itself uploads for the slice (copy: the records' bytes and the gaps), and
+ * for QUIC open the header step, between the descriptor uploads and the kernels, where they always were queued.
+ * An AES-GCM slice is planned like a batch (lanes: mapped_lanes or choose_lanes; chunks; the order, uploaded only when it is
+ * not the identity); a ChaCha slice has no launch plan (the kernels take the records in descriptor order, as in run_batch: no
+ * chunks, no order, no chunk queue), only chacha_plan's width and layout.
+ * The ALIGNED kernels also need 16-byte aligned bases, which launch_plan tests.  The mapped transport's are the caller's
+ * buffers; the copy transport's are hipMalloc'd staging, always aligned (its slice-local offsets keep the caller's alignment
+ * modulo 16, slice_plan.cpp), so there the descriptors alone decide, as they always did. */
+template <class Hook>
+static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, const ModeInfo &m, const uint8_t *in,
+                        const uint8_t *aad, uint8_t *out, uint64_t *result, ptls_hip_keyset_t *hp_ks, bool have_supp, uint8_t *mask,
+                        bool mapped, Hook hook)
 {
-    if (ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305)
-        return launch_chacha_slice(p, s, ks, cnt, chacha_plan(p, s.h_recs, cnt, mapped), m, in, aad, out, result, hp_ks, have_supp,
-                                   mask, payload);
     const unsigned ncu = (unsigned)p->eng->ncu;
-    const std::vector<Chunk> &ch = p->ch;
-    bool aligned;
-    build_chunks(s.h_recs, cnt, lanes, ncu, p->ch, p->order, aligned);
-    std::memcpy(s.h_chunks, ch.data(), ch.size() * sizeof(Chunk));
-    const bool ident = identity_order(p->order, cnt);
-    if (!ident) {
-        std::memcpy(s.h_order, p->order.data(), cnt * sizeof(uint32_t));
-        for (size_t t = 0; t < cnt; ++t)
-            s.h_recs_ord[t] = s.h_recs[p->order[t]];
-        HIP_TRY(hipMemcpyAsync(s.d_recs_ord, s.h_recs_ord, cnt * sizeof(ptls_hip_record_t), hipMemcpyHostToDevice, s.stream),
-                PTLS_HIP_ENODEV);
-        HIP_TRY(hipMemcpyAsync(s.d_order, s.h_order, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    LaunchPlan lp{};
+    lp.eng = p->eng;
+    lp.n = cnt;
+    lp.d_recs = s.d_recs;
+    lp.ncus = ncu;
+    const bool chacha = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
+    if (chacha) {
+        const ChaChaPlan c = chacha_plan(p, s.h_recs, cnt, mapped);
+        lp.chacha_lanes = c.lanes;
+        lp.chacha_runs = c.runs; /* (all_aligned: below) */
+    } else {
+        lp.lanes = mapped ? mapped_lanes(s.h_recs, cnt, ncu) : choose_lanes(s.h_recs, cnt, ncu);
+        build_chunks(s.h_recs, cnt, lp.lanes, ncu, p->ch, p->order, lp.all_aligned);
+        lp.wg = plan_wg(p->ch, lp.lanes);
+        lp.d_chunks = s.d_chunks;
+        lp.nchunks = (uint32_t)p->ch.size();
+        std::memcpy(s.h_chunks, p->ch.data(), p->ch.size() * sizeof(Chunk));
+        if (!identity_order(p->order, cnt)) {
+            lp.d_recs_ord = s.d_recs_ord;
+            lp.d_order = s.d_order;
+            std::memcpy(s.h_order, p->order.data(), cnt * sizeof(uint32_t));
+            for (size_t t = 0; t < cnt; ++t)
+                s.h_recs_ord[t] = s.h_recs[p->order[t]];
+            HIP_TRY(hipMemcpyAsync(s.d_recs_ord, s.h_recs_ord, cnt * sizeof(ptls_hip_record_t), hipMemcpyHostToDevice, s.stream),
+                    PTLS_HIP_ENODEV);
+            HIP_TRY(hipMemcpyAsync(s.d_order, s.h_order, cnt * sizeof(uint32_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+        }
     }
     HIP_TRY(hipMemcpyAsync(s.d_recs, s.h_recs, cnt * sizeof(ptls_hip_record_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-    HIP_TRY(hipMemcpyAsync(s.d_chunks, s.h_chunks, ch.size() * sizeof(Chunk), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
+    if (lp.nchunks != 0)
+        HIP_TRY(hipMemcpyAsync(s.d_chunks, s.h_chunks, lp.nchunks * sizeof(Chunk), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
     if (have_supp)
         HIP_TRY(hipMemcpyAsync(s.d_supp, s.h_supp, cnt * sizeof(ptls_hip_supp_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-    if (int rc = payload())
+    if (int rc = hook(lp))
         return rc;
     const unsigned egrid = record_grid(cnt, p->eng->ncu);
     if (m.aad_in_out && !m.quic) { /* TLS 1.3 seal: the headers, which the record kernel reads back as the AAD */
@@ -394,31 +415,14 @@ static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *
         if (eh != 0)
             return fail(PTLS_HIP_ELAUNCH, "pipeline: header kernel launch failed: %s", hipGetErrorString((hipError_t)eh));
     }
-    KernelArgs a{};
-    a.recs = s.d_recs;
-    a.recs_ord = ident ? s.d_recs : s.d_recs_ord;
-    a.order = ident ? nullptr : s.d_order;
-    a.chunks = s.d_chunks;
-    a.nchunks = (uint32_t)ch.size();
-    a.in = in;
-    a.aad = m.aad_in_out ? out : m.aad_in_in ? in : aad;
-    a.out = out;
-    a.result = result;
-    set_key_args(a, p->eng, ks, hp_ks);
-    if (have_supp) {
-        a.supp = s.d_supp;
-        a.mask = mask;
-    }
-    /* the ALIGNED kernels also need 16-byte aligned bases.  The mapped transport's are the caller's buffers; the copy
-     * transport's are hipMalloc'd staging, always aligned (its slice-local offsets keep the caller's alignment modulo 16,
-     * slice_plan.cpp), so there the descriptors alone decide, as they always did. */
-    const bool base_aligned =
-        ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.aad) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0;
-    const unsigned grid = plan_grid(cnt, ch.size(), lanes, ncu);
-    a.queue = queue_slot(p->eng);
-    const int e = launch_batch(lanes, ks->key_size == 16 ? 10 : 14, m.open, plan_wg(ch, lanes), grid, s.stream, a, aligned && base_aligned);
-    if (e != 0)
-        return fail(PTLS_HIP_ELAUNCH, "pipeline: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    /* A ChaCha slice's descriptors are scanned here, behind the uploads, so that the scan overlaps them: a slice of short
+     * records is host-bound, and scanned before the uploads 4M x 256 B mapped lost 2.5 % (21.7 -> 21.1 GiB/s seal+open,
+     * profiles/launch_plan_refactor_ab.log, first series) */
+    if (chacha)
+        lp.all_aligned = offsets_aligned(s.h_recs, cnt);
+    if (int rc = launch_plan(lp, ks, in, m.aad_in_out ? out : m.aad_in_in ? in : aad, out, result, s.stream, m.open, hp_ks,
+                             have_supp ? s.d_supp : nullptr, have_supp ? mask : nullptr))
+        return rc;
     if (m.aad_in_in && !m.quic) { /* TLS 1.3 open: strip the inner plaintext's padding and content type */
         const int ei = launch_tls13_inner(s.d_recs, (uint32_t)cnt, out, result, egrid, s.stream);
         if (ei != 0)
@@ -427,51 +431,43 @@ static int launch_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *
     return 0;
 }
 
-/* The same for a ChaCha20-Poly1305 keyset: no launch plan (the kernels take the records in descriptor order, as in
- * run_batch: no chunks, no order, no chunk queue), so the descriptor uploads, the payload, and the three kernels. */
-template <class Payload>
-static int launch_chacha_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, size_t cnt, ChaChaPlan plan,
-                               const ModeInfo &m, const uint8_t *in, const uint8_t *aad, uint8_t *out, uint64_t *result,
-                               ptls_hip_keyset_t *hp_ks, bool have_supp, uint8_t *mask, Payload payload)
+/* The slice loop of every transport: slices rotate over the slots' streams, so the host plans and uploads slice k + 1
+ * while the device runs k.  Per slice: plan(i, j) cuts records [i, j) on the host alone, refusals included, while the slot's
+ * previous slice may still run; only then the slot is waited for; enqueue(s, i, j - i) fills the slot's staging and queues the
+ * slice on s.stream.  At the end every slot is waited for: a kernel's stores to host memory are complete once its stream
+ * event has been waited for.  After an error the caller drains the slots (drain_slots). */
+template <class Plan, class Enqueue>
+static int run_slices(ptls_hip_pipeline_t *p, size_t n, Plan plan, Enqueue enqueue)
 {
-    HIP_TRY(hipMemcpyAsync(s.d_recs, s.h_recs, cnt * sizeof(ptls_hip_record_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-    if (have_supp)
-        HIP_TRY(hipMemcpyAsync(s.d_supp, s.h_supp, cnt * sizeof(ptls_hip_supp_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-    if (int rc = payload())
-        return rc;
-    const unsigned egrid = record_grid(cnt, p->eng->ncu);
-    if (m.aad_in_out && !m.quic) {
-        const int eh = launch_tls13_headers(s.d_recs, (uint32_t)cnt, out, egrid, s.stream);
-        if (eh != 0)
-            return fail(PTLS_HIP_ELAUNCH, "pipeline: header kernel launch failed: %s", hipGetErrorString((hipError_t)eh));
+    int k = 0;
+    for (size_t i = 0, j = 0; i < n; i = j, ++k) {
+        if (int rc = plan(i, j))
+            return rc;
+        PipeSlot &s = p->slot[k % NSLOT];
+        if (int rc = slot_wait(s))
+            return rc;
+        if (int rc = enqueue(s, i, j - i))
+            return rc;
+        if (int rc = slot_submit(s))
+            return rc;
     }
-    ChaChaArgs a{};
-    a.recs = s.d_recs;
-    a.n = cnt;
-    a.in = in;
-    a.aad = m.aad_in_out ? out : m.aad_in_in ? in : aad;
-    a.out = out;
-    a.result = result;
-    a.slots = ks->d_chacha;
-    if (have_supp) {
-        a.supp = s.d_supp;
-        a.hp_slots = hp_ks->d_chacha;
-        a.hp_nslots = (uint32_t)hp_ks->nslots;
-        a.mask = mask;
-    }
-    bool aligned = ((reinterpret_cast<uintptr_t>(a.in) | reinterpret_cast<uintptr_t>(a.aad) | reinterpret_cast<uintptr_t>(a.out)) & 15) == 0;
-    for (size_t t = 0; t < cnt && aligned; ++t)
-        aligned = ((s.h_recs[t].in_off | s.h_recs[t].out_off | s.h_recs[t].aad_off) & 15) == 0;
-    const int e = plan.runs ? launch_chacha_runs(plan.lanes, m.open, s.stream, a, aligned)
-                            : launch_chacha_batch(plan.lanes, m.open, s.stream, a, aligned);
-    if (e != 0)
-        return fail(PTLS_HIP_ELAUNCH, "pipeline: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (m.aad_in_in && !m.quic) {
-        const int ei = launch_tls13_inner(s.d_recs, (uint32_t)cnt, out, result, egrid, s.stream);
-        if (ei != 0)
-            return fail(PTLS_HIP_ELAUNCH, "pipeline: inner-plaintext kernel launch failed: %s", hipGetErrorString((hipError_t)ei));
-    }
+    for (auto &s : p->slot)
+        if (int rc = slot_wait(s))
+            return rc;
     return 0;
+}
+
+/* the mapped transports' greedy cut from record i: at most `cap` records and 4 x slice_bytes of payload.  4 x the staging
+ * slice: no staging is involved, and the measured best (seal+open GiB/s of 1 GiB, 64 / 128 / 256 / 512 / 2048 MiB slices:
+ * 16-KiB records 35.5 / 38.6 / 39.8 / 39.9 / 39.6, 1350-B records 32.9 / 33.3 / 33.4 / 30.7 / 21.9, configs[3] 34.7 / 36.3 /
+ * 37.2 / 35.8 / 33.9) */
+static size_t mapped_cut(const ptls_hip_pipeline_t *p, const ptls_hip_record_t *recs, size_t n, size_t i, size_t cap)
+{
+    const size_t mslice = 4 * p->slice_bytes;
+    size_t cnt = 0, bytes = 0;
+    while (i + cnt < n && cnt < cap && (cnt == 0 || bytes + recs[i + cnt].len <= mslice))
+        bytes += recs[i + cnt++].len;
+    return i + cnt;
 }
 
 /* PTLS_HIP_TRANSPORT_MAPPED: the batch kernel reads the records from, and writes them to, the caller's pinned host
@@ -484,39 +480,23 @@ static int pipeline_run_mapped(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, co
                                const uint8_t *d_in, const uint8_t *d_aad, uint8_t *d_out, uint64_t *h_result, uint64_t *d_res,
                                const ModeInfo &m, ptls_hip_keyset_t *hp_ks, const ptls_hip_supp_t *supp, uint8_t *d_mask)
 {
-    /* 4 x the staging slice: no staging is involved, and the measured best (seal+open GiB/s of 1 GiB, 64 / 128 /
-     * 256 / 512 / 2048 MiB slices: 16-KiB records 35.5 / 38.6 / 39.8 / 39.9 / 39.6, 1350-B records 32.9 / 33.3 /
-     * 33.4 / 30.7 / 21.9, configs[3] 34.7 / 36.3 / 37.2 / 35.8 / 33.9) */
-    const size_t mslice = 4 * p->slice_bytes;
-    int k = 0;
-    for (size_t i = 0; i < n; ++k) {
-        /* slices of at most mslice bytes of payload: the host plans and uploads slice k + 1 while the device runs k */
-        size_t cnt = 0, bytes = 0;
-        while (i + cnt < n && cnt < p->max_recs - 1 && (cnt == 0 || bytes + recs[i + cnt].len <= mslice))
-            bytes += recs[i + cnt++].len;
-        PipeSlot &s = p->slot[k % NSLOT];
-        if (int rc = slot_wait(s))
-            return rc;
+    auto plan = [&](size_t i, size_t &j) { return j = mapped_cut(p, recs, n, i, p->max_recs - 1), 0; };
+    auto enqueue = [&](PipeSlot &s, size_t i, size_t cnt) -> int {
         std::memcpy(s.h_recs, recs + i, cnt * sizeof(ptls_hip_record_t));
         if (supp != nullptr)
             std::memcpy(s.h_supp, supp + i, cnt * sizeof(ptls_hip_supp_t));
         /* results go straight to mapped memory, or through the slot when h_result is not mapped */
         uint64_t *res = d_res != nullptr ? d_res + i : s.d_result;
-        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? mapped_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
-        if (int rc = launch_slice(p, s, ks, cnt, lanes, m, d_in, d_aad, d_out, res, hp_ks, supp != nullptr, d_mask, true,
-                                  [] { return 0; }))
+        if (int rc = launch_slice(p, s, ks, cnt, m, d_in, d_aad, d_out, res, hp_ks, supp != nullptr, d_mask, true,
+                                  [](const LaunchPlan &) { return 0; }))
             return rc;
         if (m.open && d_res == nullptr)
             HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream),
                     PTLS_HIP_ENODEV);
-        if (int rc = slot_submit(s))
-            return rc;
-        i += cnt;
-    }
-    /* the kernel's stores to host memory are complete once its stream event has been waited for */
-    for (auto &s : p->slot)
-        if (int rc = slot_wait(s))
-            return rc;
+        return 0;
+    };
+    if (int rc = run_slices(p, n, plan, enqueue))
+        return rc;
     p->last_transport = PTLS_HIP_TRANSPORT_MAPPED;
     return 0;
 }
@@ -597,24 +577,22 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
     CopyOrder ord;
     plan_copy_order(recs, n, m, ord);
     SlicePlan pl;
-    int k = 0;
-    for (size_t i = 0; i < n; i = pl.j, ++k) {
-        if (int rc = plan_copy_slice(recs, supp, n, i, m, p->slice_bytes, p->max_recs, hp_ks != nullptr ? hp_ks->nslots : 0, ord, pl))
-            return rc;
-        PipeSlot &s = p->slot[k % NSLOT];
-        if (int rc = slot_wait(s))
-            return rc;
+    auto plan = [&](size_t i, size_t &j) {
+        const int rc = plan_copy_slice(recs, supp, n, i, m, p->slice_bytes, p->max_recs, hp_ks != nullptr ? hp_ks->nslots : 0, ord, pl);
+        j = pl.j;
+        return rc;
+    };
+    auto enqueue = [&](PipeSlot &s, size_t i, size_t cnt) -> int {
         if (!pl.mask_dst.empty())
             if (int rc = slot_mask_buffer(p, s))
                 return rc;
         /* the slot's pinned staging: descriptors and mask places */
-        const size_t cnt = pl.j - i;
         std::memcpy(s.h_recs, pl.recs.data(), cnt * sizeof(ptls_hip_record_t));
         if (supp != nullptr)
             std::memcpy(s.h_supp, pl.supp.data(), cnt * sizeof(ptls_hip_supp_t));
         s.mask_host = static_cast<uint8_t *>(h_mask);
         s.mask_dst.swap(pl.mask_dst);
-        auto payload = [&]() -> int {
+        auto payload = [&](const LaunchPlan &) -> int {
             HIP_TRY(hipMemcpyAsync(s.d_in + (pl.in.lo - pl.in_base), hin + pl.in.lo, pl.in.hi - pl.in.lo, hipMemcpyHostToDevice, s.stream),
                     PTLS_HIP_ENODEV);
             if (pl.aad.hi > pl.aad.lo)
@@ -623,9 +601,7 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
                         PTLS_HIP_ENODEV);
             return stage_gaps(p, s, pl, hout);
         };
-        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
-        if (int rc = launch_slice(p, s, ks, cnt, lanes, m, s.d_in, s.d_aad, s.d_out, s.d_result, hp_ks, supp != nullptr, s.d_mask,
-                                  false, payload))
+        if (int rc = launch_slice(p, s, ks, cnt, m, s.d_in, s.d_aad, s.d_out, s.d_result, hp_ks, supp != nullptr, s.d_mask, false, payload))
             return rc;
         for (const Span &pc : pl.pieces)
             HIP_TRY(hipMemcpyAsync(hout + pc.lo, s.d_out + (pc.lo - pl.out_base), pc.hi - pc.lo, hipMemcpyDeviceToHost, s.stream),
@@ -635,13 +611,9 @@ static int pipeline_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, cons
         if (m.open) /* results come back in slice order; the caller's array is indexed like recs */
             HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream),
                     PTLS_HIP_ENODEV);
-        if (int rc = slot_submit(s))
-            return rc;
-    }
-    for (auto &s : p->slot)
-        if (int rc = slot_wait(s))
-            return rc;
-    return 0;
+        return 0;
+    };
+    return run_slices(p, n, plan, enqueue);
 }
 
 static int pipeline_run(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, const ptls_hip_record_t *recs, size_t n, const void *h_in,
@@ -690,8 +662,7 @@ static int pipeline_run(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, const ptl
         uint8_t *d_mask = static_cast<uint8_t *>(mapped_span(h_mask, need_mask, &partial));
         uint64_t *d_res = m.open ? static_cast<uint64_t *>(mapped_span(h_result, (uint64_t)n * 8, &partial)) : nullptr;
         if (partial)
-            return fail(PTLS_HIP_EINVAL, "pipeline: a host buffer is pinned or registered only in part (its mapping ends before "
-                                         "the last byte the records touch): neither transport can use it");
+            return refuse_partial();
         const bool ok = d_in != nullptr && d_out != nullptr && (h_aad == nullptr || d_aad != nullptr) && (h_mask == nullptr || d_mask != nullptr);
         if (ok && p->transport != PTLS_HIP_TRANSPORT_COPY) {
             const int rc = pipeline_run_mapped(p, ks, recs, n, d_in, d_aad, d_out, h_result, d_res, m, hp_ks, supp, d_mask);
@@ -777,52 +748,36 @@ static int slot_quic_buffers(ptls_hip_pipeline_t *p, PipeSlot &s, bool open)
  *   seal: descriptors, `upload`, the record kernel with the header-protection masks (AAD = the header in pkt, where the
  *         output goes), quic_protect_kernel;
  *   open: descriptors, `upload`, quic_unprotect_kernel (it rewrites the slice's d_recs, and d_recs_ord through d_order when
- *         the launch plan has an order: launch_slice uploaded the provisional ones before `upload`), on the copy transport
+ *         the launch plan has an order: launch_slice uploaded the provisional ones before its hook), on the copy transport
  *         quic_pack_headers_kernel (`packed`), then the record open kernel (input and AAD in pkt).
  * `upload` queues what the transport itself uploads.  in / pkt / out / result / pn_out are device addresses. */
 template <class Upload>
 static int launch_quic_slice(ptls_hip_pipeline_t *p, PipeSlot &s, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, size_t cnt,
-                             int lanes, const ModeInfo &m, const uint8_t *in, uint8_t *pkt, uint8_t *out, uint64_t *result,
-                             uint64_t *pn_out, uint8_t *packed, bool mapped, Upload upload)
+                             const ModeInfo &m, const uint8_t *in, uint8_t *pkt, uint8_t *out, uint64_t *result, uint64_t *pn_out,
+                             uint8_t *packed, bool mapped, Upload upload)
 {
     HIP_TRY(hipMemcpyAsync(s.d_pkts, s.h_pkts, cnt * sizeof(ptls_hip_quic_packet_t), hipMemcpyHostToDevice, s.stream), PTLS_HIP_ENODEV);
-    const bool chacha = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
-    /* one thread per packet; the AES unprotect kernel builds its T-tables per workgroup (the grid of quic.cpp) */
-    const size_t wgs = (cnt + 255) / 256;
-    auto between = [&]() -> int {
+    auto between = [&](const LaunchPlan &lp) -> int {
         if (int rc = upload())
             return rc;
         if (!m.open)
             return 0;
-        const bool ident = chacha || identity_order(p->order, cnt); /* (p->order: launch_slice's plan of this slice) */
-        QuicArgs a{};
-        a.pkts = s.d_pkts;
-        a.n = (uint32_t)cnt;
-        a.order = ident ? nullptr : s.d_order;
-        a.recs = s.d_recs;
-        a.recs_ord = ident ? nullptr : s.d_recs_ord;
-        a.pkt = pkt;
-        a.pn_out = pn_out;
-        a.hp_slots = hp_ks->d_slots;
-        a.hp_chacha = hp_ks->d_chacha;
-        a.t0 = p->eng->d_t0;
-        const unsigned grid = (unsigned)(chacha ? wgs : std::min<size_t>(wgs, (size_t)p->eng->ncu * 4));
-        int e = launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, a, grid, s.stream);
+        int e = quic_unprotect(p->eng, hp_ks, s.d_pkts, cnt, lp.d_recs, lp.d_recs_ord, lp.d_order, pkt, pn_out, s.stream);
         if (e == 0 && packed != nullptr)
             e = launch_quic_pack_headers(s.d_pkts, (uint32_t)cnt, pkt, packed, s.stream);
         return e == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline_quic_open: header kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     };
     if (m.open)
-        return launch_slice(p, s, ks, cnt, lanes, m, pkt, nullptr, out, result, nullptr, false, nullptr, mapped, between);
-    if (int rc = launch_slice(p, s, ks, cnt, lanes, m, in, nullptr, pkt, nullptr, hp_ks, true, s.d_mask, mapped, between))
+        return launch_slice(p, s, ks, cnt, m, pkt, nullptr, out, result, nullptr, false, nullptr, mapped, between);
+    if (int rc = launch_slice(p, s, ks, cnt, m, in, nullptr, pkt, nullptr, hp_ks, true, s.d_mask, mapped, between))
         return rc;
-    const int e = launch_quic_protect(s.d_pkts, (uint32_t)cnt, pkt, s.d_mask, (unsigned)wgs, s.stream);
+    const int e = quic_protect(s.d_pkts, cnt, pkt, s.d_mask, s.stream);
     return e == 0 ? 0 : fail(PTLS_HIP_ELAUNCH, "pipeline_quic_seal: header kernel launch failed: %s", hipGetErrorString((hipError_t)e));
 }
 
 /* the slice's descriptors into the slot's pinned staging: records and packets [i, i + cnt) in the offsets the kernels will
  * use.  open: the provisional records are marked not 16-byte aligned (the real in_off is known only to
- * quic_unprotect_kernel, and both build_chunks and launch_chacha_slice take `aligned` from these host descriptors);
+ * quic_unprotect_kernel, and launch_slice takes `all_aligned` from these host descriptors);
  * seal: mask t of the slice at 16 t of the slot's d_mask */
 static void fill_quic_slot(PipeSlot &s, const ptls_hip_record_t *recs, const ptls_hip_supp_t *supp,
                            const ptls_hip_quic_packet_t *pkts, size_t cnt, const ModeInfo &m)
@@ -848,33 +803,22 @@ static int quic_run_mapped(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_h
                            const uint8_t *d_in, uint8_t *d_pkt, uint8_t *d_out, uint64_t *h_result, uint64_t *d_res,
                            uint64_t *h_pn, uint64_t *d_pn)
 {
-    const size_t mslice = 4 * p->slice_bytes, cap = slot_max_masks(p->slice_bytes);
-    int k = 0;
-    for (size_t i = 0; i < n; ++k) {
-        size_t cnt = 0, bytes = 0;
-        while (i + cnt < n && cnt < cap && (cnt == 0 || bytes + recs[i + cnt].len <= mslice))
-            bytes += recs[i + cnt++].len;
-        PipeSlot &s = p->slot[k % NSLOT];
-        if (int rc = slot_wait(s))
-            return rc;
+    auto plan = [&](size_t i, size_t &j) { return j = mapped_cut(p, recs, n, i, slot_max_masks(p->slice_bytes)), 0; };
+    auto enqueue = [&](PipeSlot &s, size_t i, size_t cnt) -> int {
         if (int rc = slot_quic_buffers(p, s, m.open))
             return rc;
         fill_quic_slot(s, recs + i, m.open ? nullptr : supp + i, pkts + i, cnt, m);
         uint64_t *res = d_res != nullptr ? d_res + i : s.d_result, *pn = d_pn != nullptr ? d_pn + i : s.d_pn;
-        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? mapped_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
-        if (int rc = launch_quic_slice(p, s, ks, hp_ks, cnt, lanes, m, d_in, d_pkt, d_out, res, pn, nullptr, true, [] { return 0; }))
+        if (int rc = launch_quic_slice(p, s, ks, hp_ks, cnt, m, d_in, d_pkt, d_out, res, pn, nullptr, true, [] { return 0; }))
             return rc;
         if (m.open && d_res == nullptr)
             HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
         if (m.open && d_pn == nullptr)
             HIP_TRY(hipMemcpyAsync(h_pn + i, s.d_pn, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
-        if (int rc = slot_submit(s))
-            return rc;
-        i += cnt;
-    }
-    for (auto &s : p->slot)
-        if (int rc = slot_wait(s))
-            return rc;
+        return 0;
+    };
+    if (int rc = run_slices(p, n, plan, enqueue))
+        return rc;
     p->last_transport = PTLS_HIP_TRANSPORT_MAPPED;
     return 0;
 }
@@ -893,16 +837,14 @@ static int quic_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip
     CopyOrder ord;
     plan_copy_order(recs, n, m, ord);
     QuicSlicePlan pl;
-    int k = 0;
-    for (size_t i = 0; i < n; i = pl.s.j, ++k) {
-        if (int rc = plan_quic_slice(pkts, recs, supp, n, i, m, p->slice_bytes, p->max_recs, ord, pl))
-            return rc;
-        PipeSlot &s = p->slot[k % NSLOT];
-        if (int rc = slot_wait(s))
-            return rc;
+    auto plan = [&](size_t i, size_t &j) {
+        const int rc = plan_quic_slice(pkts, recs, supp, n, i, m, p->slice_bytes, p->max_recs, ord, pl);
+        j = pl.s.j;
+        return rc;
+    };
+    auto enqueue = [&](PipeSlot &s, size_t i, size_t cnt) -> int {
         if (int rc = slot_quic_buffers(p, s, m.open))
             return rc;
-        const size_t cnt = pl.s.j - i;
         fill_quic_slot(s, pl.s.recs.data(), pl.s.supp.data(), pl.pkts.data(), cnt, m);
         s.hdr_host = h_pkt;
         s.hdr_dst.swap(pl.hdr_dst);
@@ -913,8 +855,7 @@ static int quic_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip
                         PTLS_HIP_ENODEV);
             return stage_gaps(p, s, pl.s, hout);
         };
-        const int lanes = p->algo == PTLS_HIP_ALGO_AESGCM ? choose_lanes(s.h_recs, cnt, (unsigned)p->eng->ncu) : 0;
-        if (int rc = launch_quic_slice(p, s, ks, hp_ks, cnt, lanes, m, s.d_in, m.open ? s.d_in : s.d_out, s.d_out, s.d_result, s.d_pn,
+        if (int rc = launch_quic_slice(p, s, ks, hp_ks, cnt, m, s.d_in, m.open ? s.d_in : s.d_out, s.d_out, s.d_result, s.d_pn,
                                        m.open ? s.d_hdr : nullptr, false, upload))
             return rc;
         for (const Span &pc : pl.s.pieces)
@@ -925,13 +866,9 @@ static int quic_run_copy(ptls_hip_pipeline_t *p, ptls_hip_keyset_t *ks, ptls_hip
             HIP_TRY(hipMemcpyAsync(h_result + i, s.d_result, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
             HIP_TRY(hipMemcpyAsync(h_pn + i, s.d_pn, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost, s.stream), PTLS_HIP_ENODEV);
         }
-        if (int rc = slot_submit(s))
-            return rc;
-    }
-    for (auto &s : p->slot)
-        if (int rc = slot_wait(s))
-            return rc;
-    return 0;
+        return 0;
+    };
+    return run_slices(p, n, plan, enqueue);
 }
 
 /* both calls: every refusal comes before anything is launched, copied or written */
@@ -987,8 +924,7 @@ static int pipeline_quic_run(const char *who, ptls_hip_pipeline_t *p, ptls_hip_k
     uint64_t *d_res = m.open ? static_cast<uint64_t *>(mapped_span(h_result, (uint64_t)n * 8, &partial)) : nullptr;
     uint64_t *d_pn = m.open ? static_cast<uint64_t *>(mapped_span(h_pn, (uint64_t)n * 8, &partial)) : nullptr;
     if (partial)
-        return fail(PTLS_HIP_EINVAL, "pipeline: a host buffer is pinned or registered only in part (its mapping ends before "
-                                     "the last byte the records touch): neither transport can use it");
+        return refuse_partial();
     int rc;
     if (d_pkt != nullptr && d_data != nullptr && p->transport != PTLS_HIP_TRANSPORT_COPY) {
         rc = quic_run_mapped(p, ks, hp_ks, pkts, recs.data(), supp.data(), n, m, m.open ? nullptr : d_data, d_pkt,

@@ -165,6 +165,15 @@ static void guided_tail(std::vector<Chunk> &ch, uint32_t per_task, unsigned ncu)
     ch.swap(out);
 }
 
+/* what the ALIGNED kernels need of the descriptors (they also need 16-byte aligned bases: launch_plan) */
+bool offsets_aligned(const ptls_hip_record_t *recs, size_t n)
+{
+    uint64_t any = 0;
+    for (size_t i = 0; i < n; ++i)
+        any |= recs[i].in_off | recs[i].out_off | recs[i].aad_off;
+    return (any & 15) == 0;
+}
+
 /* chunk = run of records with one key slot, sized to keep all waves of a workgroup busy for a few tasks
  * (at most 32 wave tasks), but small enough that a batch of fewer tasks still spreads over every CU (the
  * grid is one workgroup per chunk up to the CU count).  Inside a chunk the records are ordered by
@@ -184,7 +193,7 @@ void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned n
         uint32_t max_len = 0;
         for (size_t i = 0; i < n; ++i) {
             order[i] = (uint32_t)i;
-            if (((recs[i].in_off | recs[i].out_off | recs[i].aad_off) & 15) != 0)
+            if (!offsets_aligned(recs + i, 1))
                 all_aligned = false;
             if (i != 0 && recs[i].len > recs[i - 1].len)
                 sorted = false;
@@ -222,7 +231,7 @@ void build_chunks(const ptls_hip_record_t *recs, size_t n, int lanes, unsigned n
         c.flags = 1;
         bool sorted = true;
         while (i < n && recs[i].key == c.key && c.count < max_chunk) {
-            if (((recs[i].in_off | recs[i].out_off | recs[i].aad_off) & 15) != 0)
+            if (!offsets_aligned(recs + i, 1))
                 c.flags = 0;
             if (c.count != 0 && recs[i].len > recs[i - 1].len)
                 sorted = false;

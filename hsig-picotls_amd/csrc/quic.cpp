@@ -138,12 +138,31 @@ static int check_call(const char *who, ptls_hip_quic_batch_t *q, bool open, ptls
     return 0;
 }
 
-/* one thread per packet; the AES kernel builds its T-tables per workgroup, so its threads take several packets each (the
- * grid of aesecb_batch_kernel) */
-static unsigned quic_grid(const ptls_hip_quic_batch_t *q, bool lds_tables)
+int quic_unprotect(ptls_hip_engine_t *eng, const ptls_hip_keyset_t *hp_ks, const ptls_hip_quic_packet_t *d_pkts, size_t n,
+                   ptls_hip_record_t *d_recs, ptls_hip_record_t *d_recs_ord, const uint32_t *d_order, void *pkt, uint64_t *pn_out,
+                   void *stream)
 {
-    const size_t wgs = (q->n + 255) / 256;
-    return (unsigned)(lds_tables ? std::min<size_t>(wgs, (size_t)q->eng->ncu * 4) : wgs);
+    const bool chacha = hp_ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
+    QuicArgs a{};
+    a.pkts = d_pkts;
+    a.n = (uint32_t)n;
+    a.order = d_order;
+    a.recs = d_recs;
+    a.recs_ord = d_recs_ord;
+    a.pkt = static_cast<uint8_t *>(pkt);
+    a.pn_out = pn_out;
+    a.hp_slots = hp_ks->d_slots;
+    a.hp_chacha = hp_ks->d_chacha;
+    a.t0 = eng->d_t0;
+    /* one thread per packet; the AES kernel builds its T-tables per workgroup, so its threads take several packets each
+     * (record_grid, the grid of aesecb_batch_kernel) */
+    const unsigned grid = chacha ? (unsigned)((n + 255) / 256) : record_grid(n, eng->ncu);
+    return launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, a, grid, stream);
+}
+
+int quic_protect(const ptls_hip_quic_packet_t *d_pkts, size_t n, void *pkt, const uint8_t *d_mask, void *stream)
+{
+    return launch_quic_protect(d_pkts, (uint32_t)n, static_cast<uint8_t *>(pkt), d_mask, (unsigned)((n + 255) / 256), stream);
 }
 
 extern "C" int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *q, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
@@ -159,7 +178,7 @@ extern "C" int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *q, ptls_hip_keyse
     if (int e = run_batch(q->inner, ks, in, pkt, pkt, nullptr, stream, false, hp_ks, q->d_supp, q->d_mask))
         return e;
     DeviceGuard g(q->eng->device);
-    const int e = launch_quic_protect(q->d_pkts, (uint32_t)q->n, static_cast<uint8_t *>(pkt), q->d_mask, quic_grid(q, false), stream);
+    const int e = quic_protect(q->d_pkts, q->n, pkt, q->d_mask, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "quic_seal_batch: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     q->uses.note(stream);
@@ -178,19 +197,8 @@ extern "C" int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *q, ptls_hip_keyse
     ptls_hip_batch_t *b = q->inner;
     {
         DeviceGuard g(q->eng->device);
-        QuicArgs a{};
-        a.pkts = q->d_pkts;
-        a.n = (uint32_t)q->n;
-        a.order = b->d_order; /* the inner batch's current plan (ptls_hip_batch_set_lanes re-plans it) */
-        a.recs = b->d_recs;
-        a.recs_ord = b->d_recs_ord;
-        a.pkt = static_cast<uint8_t *>(pkt);
-        a.pn_out = pn_out;
-        const bool chacha = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
-        a.hp_slots = hp_ks->d_slots;
-        a.hp_chacha = hp_ks->d_chacha;
-        a.t0 = q->eng->d_t0;
-        const int e = launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, a, quic_grid(q, !chacha), stream);
+        /* the inner batch's current plan (ptls_hip_batch_set_lanes re-plans it) */
+        const int e = quic_unprotect(q->eng, hp_ks, q->d_pkts, q->n, b->d_recs, b->d_recs_ord, b->d_order, pkt, pn_out, stream);
         if (e != 0)
             return fail(PTLS_HIP_ELAUNCH, "quic_open_batch: kernel launch failed: %s", hipGetErrorString((hipError_t)e));
         keyset_note_use(hp_ks, stream);

@@ -392,20 +392,7 @@ extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *
         p.d_chunks = rx->d_chunk;
         p.nchunks = 1;
     }
-    QuicArgs q{};
-    q.pkts = rx->d_packed;
-    q.n = (uint32_t)m;
-    q.order = chacha ? nullptr : rx->d_order;
-    q.recs = rx->d_recs;
-    q.recs_ord = chacha ? nullptr : rx->d_recs_ord;
-    q.pkt = static_cast<uint8_t *>(d_buf);
-    q.pn_out = d_pn_out;
-    q.hp_slots = hp_ks->d_slots;
-    q.hp_chacha = hp_ks->d_chacha;
-    q.t0 = eng->d_t0;
-    const size_t wgs = (m + 255) / 256; /* (quic.cpp quic_grid) */
-    const unsigned hgrid = (unsigned)(chacha ? wgs : std::min<size_t>(wgs, (size_t)eng->ncu * 4));
-    e = launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, q, hgrid, stream);
+    e = quic_unprotect(eng, hp_ks, rx->d_packed, m, p.d_recs, p.d_recs_ord, p.d_order, d_buf, d_pn_out, stream); /* (ChaCha: no order) */
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
     keyset_note_use(hp_ks, stream);

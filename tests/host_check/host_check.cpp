@@ -193,7 +193,22 @@ static void check_planner(std::mt19937_64 &rng, int sets)
             recs[i].aad_off = rng() % (1u << 20);
             recs[i].key = key;
         }
+        /* three sets in four have every offset on a multiple of 16, one of those but a single offset of one record */
+        if (s % 4 != 0)
+            for (auto &r : recs)
+                r.in_off &= ~15ull, r.out_off &= ~15ull, r.aad_off &= ~15ull;
+        if (s % 4 == 1 && n != 0) {
+            ptls_hip_record_t &r = recs[rng() % n];
+            (rng() % 3 == 0 ? r.in_off : rng() % 2 == 0 ? r.out_off : r.aad_off) |= 1 + rng() % 15;
+        }
         const unsigned ncu = 1 + (unsigned)(rng() % 300);
+        /* offsets_aligned is what build_chunks reports, for a batch-kernel lane count and for the sparse form */
+        for (const int l : {4, (int)SPARSE_LANES}) {
+            bool al = !offsets_aligned(recs.data(), n);
+            build_chunks(recs.data(), n, l, ncu, ch, order, al);
+            CHECK(al == offsets_aligned(recs.data(), n));
+            CHECK(al == (n == 0 || (s % 4 != 0 && s % 4 != 1)));
+        }
         const int lanes = choose_lanes(recs.data(), n, ncu);
         CHECK(lanes == 1 || lanes == 2 || lanes == 4 || lanes == 8 || lanes == 16 || lanes == 32 || lanes == SPARSE_LANES);
         bool aligned = false;
