@@ -58,6 +58,10 @@ constexpr int PURE_BLOCKS = 2; /* data blocks per lane per iteration of the bran
 #define OPEN_MUTANT 0 /* TEST-ONLY broken build (Makefile `mutants`, tests/test_gpu_open_matrix.py): 1 = open's tag compare
                          ignores tag word 2 (bytes 8..11), so a record damaged only there is accepted */
 #endif
+#ifndef SEAL_MUTANT
+#define SEAL_MUTANT 0 /* TEST-ONLY broken build (Makefile `mutants`, tests/test_gpu_seal_exact.py): 1 = seal's tag lane also
+                         stores one byte 0x00 behind the tag, at out_p + L + 16: no record's bytes change */
+#endif
 #ifndef KS_STAMPS
 #define KS_STAMPS 0 /* DIAGNOSTIC builds only (tools/keyswitch_stamps.py): every wave sums the shader cycles it spends at key
                        switches (first barrier, table build, second barrier) and in total, and within its tasks (drawing
@@ -1637,6 +1641,8 @@ __global__ void __launch_bounds__(WGT)
                     result[rec_i] = ok ? (uint64_t)L : ~(uint64_t)0;
                 } else {
                     store_full(out_p + L, tag);
+                    if (SEAL_MUTANT == 1)
+                        out_p[L + 16] = 0;
                 }
             }
             if (!OPEN && supp != nullptr) {

@@ -15,10 +15,11 @@
 #include "ptls_hip.h"
 
 /* The product build (Makefile PROD) refuses the switches that make the kernels compute something else (the TEST-ONLY
- * dealing and open-verdict mutants) or carry diagnostics (key-switch stamps): such objects are built only into mutants/
+ * dealing, open-verdict and seal-store mutants) or carry diagnostics (key-switch stamps): such objects are built only into mutants/
  * and diag/. */
 #if defined(PTLS_HIP_PRODUCT)
-#if (defined(DEAL_MUTANT) && DEAL_MUTANT) || (defined(OPEN_MUTANT) && OPEN_MUTANT) || (defined(KS_STAMPS) && KS_STAMPS)
+#if (defined(DEAL_MUTANT) && DEAL_MUTANT) || (defined(OPEN_MUTANT) && OPEN_MUTANT) || (defined(SEAL_MUTANT) && SEAL_MUTANT) || \
+    (defined(KS_STAMPS) && KS_STAMPS)
 #error "libptls_hip.so is built with a test-mutant or diagnostic switch set"
 #endif
 #endif

@@ -228,7 +228,7 @@ def test_node_fails_loudly_without_device():
 
 
 @pytest.mark.skipif(shutil.which("/opt/rocm/bin/hipcc") is None, reason="hipcc missing")
-@pytest.mark.parametrize("switch", ["DEAL_MUTANT=1", "DEAL_MUTANT=3", "OPEN_MUTANT=1", "KS_STAMPS=1"])
+@pytest.mark.parametrize("switch", ["DEAL_MUTANT=1", "DEAL_MUTANT=3", "OPEN_MUTANT=1", "SEAL_MUTANT=1", "KS_STAMPS=1"])
 def test_product_build_refuses_wrong_output_switches(switch, tmp_path):
     """the product objects are compiled with PTLS_HIP_PRODUCT (hsig-picotls_amd/Makefile PROD): a test-mutant switch
     (wrong output by design) or a diagnostic one is then a compile error, not a library"""
@@ -242,11 +242,11 @@ def test_product_build_refuses_wrong_output_switches(switch, tmp_path):
 
 def test_product_sources_carry_no_experiment_switches():
     """the product sources hold the shipping design only.  Every preprocessor conditional in them is
-    an include guard, the x86 host pause, or one of the switches the builds use: the TEST-ONLY dealing and open-verdict
-    mutants (DEAL_MUTANT, OPEN_MUTANT), the diagnostic stamp builds (KS_STAMPS, STAMP_PHASES, WORKER_STAMPS) and the product guard; the
+    an include guard, the x86 host pause, or one of the switches the builds use: the TEST-ONLY dealing, open-verdict and
+    seal-store mutants (DEAL_MUTANT, OPEN_MUTANT, SEAL_MUTANT), the diagnostic stamp builds (KS_STAMPS, STAMP_PHASES, WORKER_STAMPS) and the product guard; the
     rejected variants are measured in EXPERIMENTS.md, not kept in the code"""
     import re
-    allowed = {"PTLS_HIP_BATCH_KERNEL_H", "PTLS_HIP_INTERNAL_H", "PTLS_HIP_HOST_H", "PTLS_HIP_PLUGIN_H", "PTLS_HIP_GF128_H", "PTLS_HIP_H", "PTLS_HIP_PRODUCT", "DEAL_MUTANT", "OPEN_MUTANT",
+    allowed = {"PTLS_HIP_BATCH_KERNEL_H", "PTLS_HIP_INTERNAL_H", "PTLS_HIP_HOST_H", "PTLS_HIP_PLUGIN_H", "PTLS_HIP_GF128_H", "PTLS_HIP_H", "PTLS_HIP_PRODUCT", "DEAL_MUTANT", "OPEN_MUTANT", "SEAL_MUTANT",
                "KS_STAMPS", "STAMP_PHASES", "WORKER_STAMPS", "__x86_64__", "__i386__", "GF128_FN"}
     csrc = os.path.join(ROOT, "hsig-picotls_amd", "csrc")
     seen = set()
