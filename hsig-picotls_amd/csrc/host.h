@@ -15,7 +15,9 @@
  *   quic_parse.cpp     QUIC datagrams parsed on the device into the packet descriptors of quic.cpp, and the connection-ID map
  *                      (kernels: quic_parse_kernel.hip; the walk and the map arithmetic shared with the CPU check: quic_parse.h)
  *   quic_rx.cpp        the QUIC receive object: parsed entries kept on the device, selected, packed, planned and opened there
- *                      (kernels: quic_rx_kernel.hip; the select rule and the sums' terms shared with the CPU check: quic_rx.h)
+ *                      (kernels: quic_rx_kernel.hip; the select rule and the sums' terms shared with the CPU check: quic_rx.h),
+ *                      and on it the key chosen by Key Phase bit and the commit of key updates (kernels:
+ *                      quic_phase_kernel.hip; the rule shared with the CPU check: quic_phase.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
  *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)
@@ -395,10 +397,12 @@ void quic_batch_lanes(ptls_hip_quic_batch_t *q, int *lanes, int *chacha_lanes);
  * use.  Open (quic_unprotect_kernel, before the record open): hp_ks's algorithm and key size give the kernel; it writes
  * the packet numbers to pn_out and the real descriptors to the record plan's d_recs, and to d_recs_ord through d_order
  * where the plan has an order.  The three are taken as they are (null order: plan position = index; pn_out and d_recs are
- * indexed by packet).  Seal (quic_protect_kernel, behind the record seal that wrote the 16-byte masks d_mask). */
+ * indexed by packet).  With ph, quic_unprotect_phase_kernel: the record's key slot by the Key Phase bit (quic_phase.h) and the
+ * generation into ph->gen_out, indexed like pn_out.  Seal (quic_protect_kernel, behind the record seal that wrote the 16-byte
+ * masks d_mask). */
 int quic_unprotect(ptls_hip_engine_t *eng, const ptls_hip_keyset_t *hp_ks, const ptls_hip_quic_packet_t *d_pkts, size_t n,
                    ptls_hip_record_t *d_recs, ptls_hip_record_t *d_recs_ord, const uint32_t *d_order, void *pkt, uint64_t *pn_out,
-                   void *stream);
+                   void *stream, const QuicPhaseArgs *ph = nullptr);
 int quic_protect(const ptls_hip_quic_packet_t *d_pkts, size_t n, void *pkt, const uint8_t *d_mask, void *stream);
 
 /* ---- plugin_worker.cpp ---- */

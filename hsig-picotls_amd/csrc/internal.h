@@ -237,6 +237,41 @@ int launch_quic_unprotect(int rounds, const QuicArgs &a, unsigned grid, void *st
 int launch_quic_protect(const ptls_hip_quic_packet_t *pkts, uint32_t n, uint8_t *pkt, const uint8_t *mask, unsigned grid,
                         void *stream);
 
+/* ---- the key chosen by Key Phase bit, and key updates committed on the device (quic_phase_kernel.hip; the rule shared
+ * with the host and the CPU check: quic_phase.h) ---- */
+
+struct QuicPhaseArgs {
+    const ptls_hip_quic_keyphase_t *phase; /* per connection, indexed by the packet's key (the select rule keeps it inside) */
+    uint32_t stride;                       /* generation g of connection c: key slot c + stride * (g % 3) */
+    uint32_t *gen_out;                     /* indexed like pn_out: written */
+};
+
+/* launch_quic_unprotect with the record's key slot chosen by quic_phase.h's rule */
+int launch_quic_unprotect_phase(int rounds, const QuicArgs &a, const QuicPhaseArgs &ph, unsigned grid, void *stream);
+
+struct QuicCommitArgs {
+    ptls_hip_quic_keyphase_t *phase; /* count entries: read by the mark pass, rewritten by the apply pass */
+    uint32_t count;
+    const ptls_hip_quic_packet_t *packed; /* the selected packets' descriptors: key = the connection */
+    const uint64_t *result, *pn_out;
+    const uint32_t *gen_out;
+    uint64_t *mins;     /* 2 x count: the lowest packet number of connection c's next-generation packets at [2 c], of its
+                           current-generation packets at [2 c + 1]; UINT64_MAX between calls */
+    uint32_t *l0;       /* the scan levels over the 0 / 1 "updated" flags, as in QuicRxArgs */
+    const uint32_t *l1, *l2;
+    uint32_t *updated;  /* the updated connections, ascending */
+};
+
+/* packets per thread of the mark pass: thread t of the grid takes packets t, t + T, t + 2 T, ... (T = threads of the grid),
+ * at least this many wherever m allows, and folds successive ones that lower the same minimum before it sends an atomic */
+constexpr uint32_t QPH_MARK_PER_THREAD = 4;
+/* a thread per QPH_MARK_PER_THREAD selected packets: 64-bit integer atomicMin into mins, behind a per-lane fold and a per-wave
+ * reduction (minima of integers: the outcome does not depend on the order or the grouping) */
+int launch_quic_phase_mark(const QuicCommitArgs &a, uint32_t m, unsigned grid, void *stream);
+/* one thread per connection.  place == 0: the flag "mins[2 c] holds a packet number" into l0.  place != 0, after the scans
+ * over the flags: the entry moved on by quic_phase_apply, mins reset, and an updated connection listed at its position */
+int launch_quic_phase_apply(const QuicCommitArgs &a, int place, unsigned grid, void *stream);
+
 /* quic_slice_kernel.hip, behind launch_quic_unprotect on a copy-transport slice: 8 bytes per packet at packed + 8 t = the
  * count of unprotected header bytes (0 with PTLS_HIP_QUIC_UNPROTECTED, else 1 + pn_len), the first byte, the packet-number
  * bytes, read from the packets at pkt */

@@ -140,7 +140,7 @@ static int check_call(const char *who, ptls_hip_quic_batch_t *q, bool open, ptls
 
 int quic_unprotect(ptls_hip_engine_t *eng, const ptls_hip_keyset_t *hp_ks, const ptls_hip_quic_packet_t *d_pkts, size_t n,
                    ptls_hip_record_t *d_recs, ptls_hip_record_t *d_recs_ord, const uint32_t *d_order, void *pkt, uint64_t *pn_out,
-                   void *stream)
+                   void *stream, const QuicPhaseArgs *ph)
 {
     const bool chacha = hp_ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
     QuicArgs a{};
@@ -157,7 +157,8 @@ int quic_unprotect(ptls_hip_engine_t *eng, const ptls_hip_keyset_t *hp_ks, const
     /* one thread per packet; the AES kernel builds its T-tables per workgroup, so its threads take several packets each
      * (record_grid, the grid of aesecb_batch_kernel) */
     const unsigned grid = chacha ? (unsigned)((n + 255) / 256) : record_grid(n, eng->ncu);
-    return launch_quic_unprotect(chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14, a, grid, stream);
+    const int rounds = chacha ? 0 : hp_ks->key_size == 16 ? 10 : 14;
+    return ph != nullptr ? launch_quic_unprotect_phase(rounds, a, *ph, grid, stream) : launch_quic_unprotect(rounds, a, grid, stream);
 }
 
 int quic_protect(const ptls_hip_quic_packet_t *d_pkts, size_t n, void *pkt, const uint8_t *d_mask, void *stream)

@@ -5,6 +5,8 @@
  * select rule and the sums' terms quic_rx.h's (shared with quic_rx_kernel.hip), the lane rules planner.cpp's, the record
  * launch batch.cpp's run_plan.  Where the planner wants the batch kernel (long key runs) the packed descriptors go back to
  * the host and through ptls_hip_quic_batch_new / ptls_hip_quic_open_batch as they are.
+ * The same open call with the key chosen by Key Phase bit, and the commit of key updates (2j): the rule is
+ * quic_phase.h's, the kernels quic_phase_kernel.hip's.
  */
 #include <algorithm>
 #include <cstdio>
@@ -18,7 +20,7 @@
 namespace {
 
 thread_local bool g_timing = false;
-thread_local float g_select_ms = 0, g_plan_ms = 0;
+thread_local float g_select_ms = 0, g_plan_ms = 0, g_header_ms = 0, g_commit_ms = 0;
 
 size_t sort_tiles(size_t m)
 {
@@ -48,7 +50,13 @@ struct st_ptls_hip_quic_rx_t {
     uint64_t *d_stats = nullptr;
     Chunk *d_chunk = nullptr;
     size_t order_n = 0; /* != 0: d_order holds the last device-made AES plan order of that many packets */
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    /* the commit's scratch (kp_cap connections): the two minima per connection, UINT64_MAX between calls; the scan levels */
+    uint64_t *d_kp_mins = nullptr;
+    uint32_t *d_kp_levels = nullptr;
+    size_t kp_cap = 0;
+    bool kp_open = false; /* the last open call was rx_open_keyphase: d_packed holds its kp_m selected packets */
+    size_t kp_m = 0;
+    hipEvent_t ev[8] = {}; /* select 0-1, sort 2-3, header kernel 4-5, commit 6-7 */
     Uses uses; /* the launches that read or write the arrays above: rx_free waits for them */
 
     template <class T>
@@ -100,7 +108,8 @@ extern "C" void ptls_hip_quic_rx_free(ptls_hip_quic_rx_t *rx)
     if (rx == nullptr)
         return;
     void *const mem[] = {rx->d_pkts,  rx->d_info,     rx->d_dgrams, rx->d_parse_levels, rx->d_sel_levels, rx->d_packed, rx->d_keys,
-                         rx->d_recs,  rx->d_recs_ord, rx->d_order,  rx->d_order_tmp,    rx->d_hist,       rx->d_stats,  rx->d_chunk};
+                         rx->d_recs,  rx->d_recs_ord, rx->d_order,  rx->d_order_tmp,    rx->d_hist,       rx->d_stats,  rx->d_chunk,
+                         rx->d_kp_mins, rx->d_kp_levels};
     bool any = false;
     for (void *p : mem)
         any = any || p != nullptr;
@@ -133,6 +142,7 @@ extern "C" int ptls_hip_quic_rx_parse(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
     rx->n = 0;
     rx->has_info = true;
     rx->order_n = 0;
+    rx->kp_open = false;
     *n_pkts = 0;
     if (n == 0)
         return 0;
@@ -177,6 +187,7 @@ extern "C" int ptls_hip_quic_rx_set_packets(ptls_hip_quic_rx_t *rx, const ptls_h
     rx->n = 0;
     rx->has_info = d_info != nullptr;
     rx->order_n = 0;
+    rx->kp_open = false;
     if (n == 0)
         return 0;
     DeviceGuard g(rx->eng->device);
@@ -228,6 +239,14 @@ extern "C" void ptls_hip_quic_rx_timing(int enable, float *select_ms, float *pla
         *plan_ms = g_plan_ms;
 }
 
+extern "C" void ptls_hip_quic_rx_keyphase_timing(float *header_ms, float *commit_ms)
+{
+    if (header_ms != nullptr)
+        *header_ms = g_header_ms;
+    if (commit_ms != nullptr)
+        *commit_ms = g_commit_ms;
+}
+
 /* one stable radix pass over m positions: counts, their scan, placement */
 static int radix_pass(ptls_hip_quic_rx_t *rx, const uint32_t *src, uint32_t m, uint32_t shift, uint32_t *dst, void *stream)
 {
@@ -259,20 +278,31 @@ static int open_on_host(ptls_hip_quic_rx_t *rx, size_t m, ptls_hip_keyset_t *ks,
     return rc;
 }
 
-extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, uint32_t type_mask,
-                                     void *d_buf, size_t buf_len, void *d_out, size_t out_len, uint32_t *d_sel, uint64_t *d_result,
-                                     uint64_t *d_pn_out, ptls_hip_quic_rx_report_t *report, void *stream)
+/* both open calls; kp == nullptr: ptls_hip_quic_rx_open */
+static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, uint32_t type_mask,
+                   const ptls_hip_quic_rx_keyphase_t *kp, void *d_buf, size_t buf_len, void *d_out, size_t out_len, uint32_t *d_sel,
+                   uint64_t *d_result, uint64_t *d_pn_out, ptls_hip_quic_rx_report_t *report, void *stream)
 {
-    const char *who = "quic_rx_open";
     if (rx == nullptr || ks == nullptr || hp_ks == nullptr || report == nullptr)
         return fail(PTLS_HIP_EINVAL, "%s: null receive object, keyset or report", who);
+    if (kp != nullptr) {
+        if (kp->d_phase == nullptr || kp->d_gen_out == nullptr)
+            return fail(PTLS_HIP_EINVAL, "%s: null key-phase state or generation array", who);
+        if (kp->stride == 0 || kp->count == 0)
+            return fail(PTLS_HIP_EINVAL, "%s: a bank stride or a state count of 0", who);
+        if (rx->mode == 2)
+            return fail(PTLS_HIP_EINVAL, "%s: the host plan (rx_set_plan 2) fixes a chunk's key on the host", who);
+    }
     if (ks->eng != rx->eng || hp_ks->eng != rx->eng)
         return fail(PTLS_HIP_EINVAL, "%s: receive object and keysets must belong to the same engine", who);
     if (hp_ks->algo != ks->algo || hp_ks->key_size != ks->key_size)
         return fail(PTLS_HIP_EINVAL, "%s: the header-protection keyset must be of the AEAD keyset's algorithm and key size", who);
+    if (kp != nullptr && kp->stride > ks->nslots / 3) /* (3 * stride <= nslots, without the product) */
+        return fail(PTLS_HIP_EINVAL, "%s: three banks of stride %zu do not fit the keyset's %zu slots", who, kp->stride, ks->nslots);
     report->n_selected = 0;
     report->planned_on_device = 0;
     report->lanes = 0;
+    rx->kp_open = false;
     if (rx->n == 0)
         return 0;
     if (d_buf == nullptr || d_out == nullptr || d_sel == nullptr || d_result == nullptr || d_pn_out == nullptr)
@@ -307,7 +337,7 @@ extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *
     QuicRxLimits lim{};
     lim.buf_len = buf_len;
     lim.out_len = out_len;
-    lim.nslots = ks->nslots;
+    lim.nslots = kp != nullptr ? std::min(kp->stride, kp->count) : ks->nslots; /* (the state is indexed by the key) */
     lim.hp_nslots = hp_ks->nslots;
     lim.type_mask = type_mask;
     lim.has_info = rx->has_info ? 1u : 0u;
@@ -344,6 +374,8 @@ extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *
         g_select_ms = rx->between(0, 1), g_plan_ms = 0;
     const size_t m = (size_t)st[QRX_STAT_COUNT];
     report->n_selected = m;
+    rx->kp_open = kp != nullptr;
+    rx->kp_m = m;
     if (m == 0)
         return 0;
 
@@ -351,7 +383,8 @@ extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *
     const bool chacha = ks->algo == PTLS_HIP_ALGO_CHACHA20POLY1305;
     const int lanes = choose_lanes_from((double)st[QRX_STAT_GHASH], m, (size_t)st[QRX_STAT_RUNS] + 1, (unsigned)eng->ncu);
     const int chacha_lanes = choose_chacha_lanes_from((double)st[QRX_STAT_BLOCKS64], m, (unsigned)eng->ncu);
-    const bool on_device = rx->mode == 1 || (rx->mode == 0 && (chacha || lanes == SPARSE_LANES));
+    /* with a key per record (kp) only the two kernels that read rec.key per record can run: always the device plan */
+    const bool on_device = kp != nullptr || rx->mode == 1 || (rx->mode == 0 && (chacha || lanes == SPARSE_LANES));
     if (!on_device)
         return open_on_host(rx, m, ks, hp_ks, d_buf, d_out, d_result, d_pn_out, report, stream);
 
@@ -392,9 +425,20 @@ extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *
         p.d_chunks = rx->d_chunk;
         p.nchunks = 1;
     }
-    e = quic_unprotect(eng, hp_ks, rx->d_packed, m, p.d_recs, p.d_recs_ord, p.d_order, d_buf, d_pn_out, stream); /* (ChaCha: no order) */
+    QuicPhaseArgs ph{};
+    if (kp != nullptr) {
+        ph.phase = kp->d_phase;
+        ph.stride = (uint32_t)kp->stride; /* 3 * stride <= nslots < 2^32 */
+        ph.gen_out = kp->d_gen_out;
+    }
+    if (kp != nullptr)
+        rx->mark(4, s);
+    e = quic_unprotect(eng, hp_ks, rx->d_packed, m, p.d_recs, p.d_recs_ord, p.d_order, d_buf, d_pn_out, stream, /* (ChaCha: no order) */
+                       kp != nullptr ? &ph : nullptr);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    if (kp != nullptr)
+        rx->mark(5, s);
     keyset_note_use(hp_ks, stream);
     rx->uses.note(stream);
     if (int rc = run_plan(p, ks, d_buf, d_buf, d_out, d_result, stream, true))
@@ -406,7 +450,102 @@ extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *
         (void)hipEventSynchronize(rx->ev[3]);
         g_plan_ms = rx->between(2, 3);
     }
+    if (g_timing && kp != nullptr && rx->ev[5] != nullptr) { /* (likewise: it waits for the header kernel) */
+        (void)hipEventSynchronize(rx->ev[5]);
+        g_header_ms = rx->between(4, 5);
+    }
     report->planned_on_device = 1;
     report->lanes = chacha ? chacha_lanes : SPARSE_LANES;
+    return 0;
+}
+
+extern "C" int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, uint32_t type_mask,
+                                     void *d_buf, size_t buf_len, void *d_out, size_t out_len, uint32_t *d_sel, uint64_t *d_result,
+                                     uint64_t *d_pn_out, ptls_hip_quic_rx_report_t *report, void *stream)
+{
+    return rx_open("quic_rx_open", rx, ks, hp_ks, type_mask, nullptr, d_buf, buf_len, d_out, out_len, d_sel, d_result, d_pn_out, report,
+                   stream);
+}
+
+extern "C" int ptls_hip_quic_rx_open_keyphase(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                                              uint32_t type_mask, const ptls_hip_quic_rx_keyphase_t *kp, void *d_buf, size_t buf_len,
+                                              void *d_out, size_t out_len, uint32_t *d_sel, uint64_t *d_result, uint64_t *d_pn_out,
+                                              ptls_hip_quic_rx_report_t *report, void *stream)
+{
+    const char *who = "quic_rx_open_keyphase";
+    if (kp == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null key-phase parameters", who);
+    return rx_open(who, rx, ks, hp_ks, type_mask, kp, d_buf, buf_len, d_out, out_len, d_sel, d_result, d_pn_out, report, stream);
+}
+
+extern "C" int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip_quic_keyphase_t *d_phase, size_t count,
+                                                const uint64_t *d_result, const uint64_t *d_pn_out, const uint32_t *d_gen_out,
+                                                uint32_t *d_updated, size_t *n_updated, void *stream)
+{
+    const char *who = "quic_rx_keyphase_commit";
+    if (rx == nullptr || d_phase == nullptr || d_result == nullptr || d_pn_out == nullptr || d_gen_out == nullptr ||
+        d_updated == nullptr || n_updated == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null receive object, state, array or n_updated", who);
+    if (count == 0 || count > 0xffffffffu)
+        return fail(PTLS_HIP_EINVAL, "%s: a state count of %zu is outside 1 .. 2^32 - 1", who, count);
+    if (!rx->kp_open)
+        return fail(PTLS_HIP_EINVAL, "%s: no rx_open_keyphase on the object since its entries were loaded or since a plain rx_open", who);
+    *n_updated = 0;
+    const size_t m = rx->kp_m;
+    if (m == 0)
+        return 0; /* nothing was selected: no entry changes */
+
+    ptls_hip_engine_t *eng = rx->eng;
+    DeviceGuard g(eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (count > rx->kp_cap) { /* (grown: the launches that used the smaller arrays are waited for first) */
+        if (rx->d_kp_mins != nullptr || rx->d_kp_levels != nullptr) {
+            rx->uses.wait();
+            dev_free(eng, rx->d_kp_mins);
+            dev_free(eng, rx->d_kp_levels);
+            rx->d_kp_mins = nullptr, rx->d_kp_levels = nullptr, rx->kp_cap = 0;
+        }
+        int e = rx->ensure(&rx->d_kp_mins, 2 * count * sizeof(uint64_t));
+        if (e == 0)
+            e = rx->ensure(&rx->d_kp_levels, scan_levels(nullptr, count).words * sizeof(uint32_t));
+        if (e != 0)
+            return e;
+        HIP_TRY(hipMemsetAsync(rx->d_kp_mins, 0xff, 2 * count * sizeof(uint64_t), s), PTLS_HIP_ENODEV); /* once: UINT64_MAX */
+        rx->kp_cap = count;
+    }
+    const ScanLevels L = scan_levels(rx->d_kp_levels, count);
+    QuicCommitArgs a{};
+    a.phase = d_phase;
+    a.count = (uint32_t)count;
+    a.packed = rx->d_packed;
+    a.result = d_result;
+    a.pn_out = d_pn_out;
+    a.gen_out = d_gen_out;
+    a.mins = rx->d_kp_mins;
+    a.l0 = L.l0;
+    a.l1 = L.has1 ? L.l1 : nullptr;
+    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.updated = d_updated;
+    /* the mark pass: QPH_MARK_PER_THREAD packets per thread, so that a lane has successive packets to fold (internal.h) */
+    const unsigned pkt_grid = quic_scan_grid((m + 256 * QPH_MARK_PER_THREAD - 1) / (256 * QPH_MARK_PER_THREAD), eng->ncu);
+    const unsigned conn_grid = quic_scan_grid((count + 255) / 256, eng->ncu);
+    rx->mark(6, s);
+    int e = launch_quic_phase_mark(a, (uint32_t)m, pkt_grid, stream);
+    if (e == 0)
+        e = launch_quic_phase_apply(a, 0, conn_grid, stream);
+    if (e == 0)
+        e = launch_scan_levels(L, eng->ncu, stream);
+    if (e == 0)
+        e = launch_quic_phase_apply(a, 1, conn_grid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    rx->uses.note(stream);
+    rx->mark(7, s);
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, L.total, sizeof(total), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
+    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    if (g_timing)
+        g_commit_ms = rx->between(6, 7);
+    *n_updated = total;
     return 0;
 }

@@ -48,6 +48,10 @@ assert QUIC_PKTINFO_DTYPE.itemsize == 32
 (QUIC_STATUS_OK, QUIC_STATUS_TRUNCATED, QUIC_STATUS_TOO_SHORT, QUIC_STATUS_BAD_CID_LEN, QUIC_STATUS_BAD_FIXED_BIT) = range(5)
 QUIC_INFO_MORE = 1
 QUIC_NO_CONN = 0xFFFFFFFF
+# ptls_hip_quic_keyphase_t: a connection's receive key-phase state (generation g of connection c: key slot c + stride * (g % 3))
+QUIC_KEYPHASE_DTYPE = np.dtype([("first_pn", "<u8"), ("gen", "<u4"), ("reserved", "<u4")])
+assert QUIC_KEYPHASE_DTYPE.itemsize == 16
+QUIC_NO_GEN = 0xFFFFFFFF
 EINVAL = -1
 
 
@@ -124,6 +128,10 @@ SIGNATURES = {
     "ptls_hip_quic_rx_set_plan": (_i, [_vp, _i]),
     "ptls_hip_quic_rx_order": (_vp, [_vp]),
     "ptls_hip_quic_rx_timing": (None, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "ptls_hip_quic_rx_open_keyphase": (_i, [_vp, _vp, _vp, ctypes.c_uint32, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
+    "ptls_hip_quic_rx_keyphase_commit": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_sz), _vp]),
+    # diagnostic only (tools/bench_quic_keyphase.py): HIP-event times of the last header kernel and commit
+    "ptls_hip_quic_rx_keyphase_timing": (None, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -565,6 +573,11 @@ class QuicRxReport(ctypes.Structure):
     _fields_ = [("n_selected", ctypes.c_uint64), ("planned_on_device", ctypes.c_int32), ("lanes", ctypes.c_int32)]
 
 
+class QuicRxKeyphase(ctypes.Structure):
+    """ptls_hip_quic_rx_keyphase_t"""
+    _fields_ = [("d_phase", ctypes.c_void_p), ("count", ctypes.c_size_t), ("stride", ctypes.c_size_t), ("d_gen_out", ctypes.c_void_p)]
+
+
 class QuicRx:
     """the receive object (ptls_hip_quic_rx_*): parsed entries stay on the device; open() selects, packs, plans and opens
     them there.  Calls on one QuicRx must be ordered (same stream)."""
@@ -633,6 +646,25 @@ class QuicRx:
                                            _ptr(d_sel), _ptr(d_result), _ptr(d_pn_out), ctypes.addressof(rep), _stream(stream)),
                "quic_rx_open")
         return rep
+
+    def open_keyphase(self, keyset, hp_keyset, d_phase, count, stride, d_gen_out, d_buf, buf_len, d_out, out_len, d_sel, d_result,
+                      d_pn_out, type_mask=QUIC_ALL_TYPES, stream=None):
+        """open() with the key slot of every short-header packet chosen on the device: key + stride * (g % 3), g from the
+        unmasked Key Phase bit and d_phase[key] (device, `count` QUIC_KEYPHASE_DTYPE entries); d_gen_out[j] = g, or QUIC_NO_GEN
+        for a long header"""
+        rep, kp = QuicRxReport(), QuicRxKeyphase(_ptr(d_phase), count, stride, _ptr(d_gen_out))
+        _check(lib().ptls_hip_quic_rx_open_keyphase(self.ptr, keyset.ptr, hp_keyset.ptr, type_mask, ctypes.addressof(kp), _ptr(d_buf),
+                                                    buf_len, _ptr(d_out), out_len, _ptr(d_sel), _ptr(d_result), _ptr(d_pn_out),
+                                                    ctypes.addressof(rep), _stream(stream)), "quic_rx_open_keyphase")
+        return rep
+
+    def keyphase_commit(self, d_phase, count, d_result, d_pn_out, d_gen_out, d_updated, stream=None):
+        """after open_keyphase with the same arrays: advances d_phase from the authenticated results on the device, lists the
+        updated connections in d_updated (device, uint32, ascending) and returns their number"""
+        n = ctypes.c_size_t(0)
+        _check(lib().ptls_hip_quic_rx_keyphase_commit(self.ptr, _ptr(d_phase), count, _ptr(d_result), _ptr(d_pn_out), _ptr(d_gen_out),
+                                                      _ptr(d_updated), ctypes.byref(n), _stream(stream)), "quic_rx_keyphase_commit")
+        return n.value
 
     def close(self):
         if self.ptr:

@@ -515,8 +515,9 @@ ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *batch);
  * Received datagrams are split into these descriptors on the device by ptls_hip_quic_parse_datagrams (2h): coalesced
  * packets, the long-header fields up to pn_offset and pkt_len, and the key slot from the Destination Connection ID.
  * Out of scope: the node API (2d); handling Retry and Version Negotiation packets (they carry no packet protection; 2h
- * reports them and the host answers); choosing the key by key phase on the device (the AES planner needs every packet's
- * key slot on the host; 2i plans on the device where the kernel's plan does not depend on the keys). */
+ * reports them and the host answers); choosing the key by key phase in these batches (the AES planner needs every packet's
+ * key slot on the host; 2i plans on the device where the kernel's plan does not depend on the keys, and 2j chooses the key by
+ * Key Phase bit there). */
 int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
                              void *pkt, void *stream);
 int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, void *pkt, void *out,
@@ -540,7 +541,8 @@ int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks
  * update_quic_secrets: the key update of RFC 9001 §6.  Every secret becomes HKDF-Expand-Label(secret, "<p> ku", "",
  *   hash_size) -- written back to `secrets` -- and ks is re-keyed from the new secret.  The header-protection key does not
  *   change with a key update, so there is no hp_ks.  A receiver keeps one keyset per key phase and updates the one of the
- *   next phase.
+ *   next phase; or, for the device-side choice of 2j, three banks of one keyset (slot c + stride * (generation % 3)) and
+ *   updates the range of the bank the oldest generation has left.
  * set_quic_initial: the Initial keys of RFC 9001 §5.2.  `dcids` = count client Destination Connection IDs at a 20-byte
  *   stride in host memory, dcid_lens[i] = 0..20 the length of each; `salt` (1..64 bytes) is the version's initial salt,
  *   supplied by the caller: 38762cf7f55934b34d179ae6a4c80cadccbb7f0a for QUIC v1 (RFC 9001 §5.2), with labels V1;
@@ -775,8 +777,9 @@ void ptls_hip_quic_parse_timing(int enable, float *kernels_ms, float *d2h_ms);
  *   stable order of the selected packets by decreasing (pkt_len - pn_offset - 17) >> 4), else NULL.
  * rx_timing: diagnostic (tools/bench_quic_rx.py), as ptls_hip_quic_parse_timing: HIP-event times of the last rx_open's
  *   select / scan / compact / sums launches and of its sort launches.
- * Out of scope: key-run chunks for the AES batch kernel made on the device; grouping interleaved packets by key; the key
- * phase; key slots for Initial packets of unknown connections; the host pipelines (2g) and the node API (2d). */
+ * Out of scope: key-run chunks for the AES batch kernel made on the device; grouping interleaved packets by key; key slots
+ * for Initial packets of unknown connections; the host pipelines (2g) and the node API (2d).  The key phase: rx_open takes
+ * `key` as it is; rx_open_keyphase (2j) chooses the generation on the device. */
 typedef struct st_ptls_hip_quic_rx_t ptls_hip_quic_rx_t;
 typedef struct st_ptls_hip_quic_rx_report_t {
     uint64_t n_selected;
@@ -799,6 +802,82 @@ int ptls_hip_quic_rx_open(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hi
 int ptls_hip_quic_rx_set_plan(ptls_hip_quic_rx_t *rx, int mode);
 const uint32_t *ptls_hip_quic_rx_order(ptls_hip_quic_rx_t *rx);
 void ptls_hip_quic_rx_timing(int enable, float *select_ms, float *plan_ms);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2j. receive keys chosen by Key Phase bit on the device, and key updates committed there        *
+ *     (RFC 9001 §6)                                                                              *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The Key Phase bit (0x04 of a short header's first byte) sits under header protection, and with 2f the header-protection
+ * keys exist only in a device keyset: the host cannot see the bit.  rx_open_keyphase is rx_open with the AEAD key slot of
+ * every short-header packet chosen by the header kernel from that bit and a small per-connection state in device memory;
+ * rx_keyphase_commit moves that state on from the authenticated results, so that the next call chooses correctly without
+ * the host having looked at a packet.
+ *
+ * The state is a caller-owned DEVICE array of 16-byte entries, indexed by the connection number that the parse call writes
+ * into `key`.  The keys of generation g of connection c live in slot c + stride * (g % 3) of ONE AEAD keyset with at least
+ * 3 * stride slots: three banks hold the previous, the current and the next generation, and the keys of generation g + 2
+ * overwrite those of g - 1 (RFC 9001 §6.5).  The header-protection key does not change with a key update: hp_ks and hp_key
+ * are used as they are. */
+typedef struct st_ptls_hip_quic_keyphase_t {
+    uint64_t first_pn; /* lowest packet number opened under the current generation; UINT64_MAX: none yet */
+    uint32_t gen;      /* generation of the current receive keys (<= 2^32 - 2); its Key Phase bit is gen & 1 */
+    uint32_t reserved; /* 0 */
+} ptls_hip_quic_keyphase_t;
+#define PTLS_HIP_QUIC_NO_GEN 0xffffffffu
+
+/* rx_open_keyphase: for a short-header packet, with `bit` the unmasked Key Phase bit (with PTLS_HIP_QUIC_UNPROTECTED: the bit
+ *   of the first byte as it stands) and pn the decoded full packet number,
+ *       g' = gen        if bit == (gen & 1)
+ *          = gen - 1    else if gen > 0 and pn < first_pn    (a reordered packet from before the update)
+ *          = gen + 1    otherwise                            (the peer has updated)
+ *   and the packet is opened under slot key + stride * (g' % 3); d_gen_out[j] = g'.  first_pn == UINT64_MAX makes every
+ *   packet with the other bit a previous-generation packet (right after a locally initiated update, before the peer has
+ *   answered); gen == 0 has no previous generation.  A long-header packet (0x80 set) is opened under slot `key` itself and
+ *   gets d_gen_out[j] = PTLS_HIP_QUIC_NO_GEN, whatever its low bits are.  Exactly one key is tried per packet: a packet sealed
+ *   under any other generation fails (UINT64_MAX), with d_gen_out[j] still the rule's value.
+ *   Everything else is rx_open's, with one change to the select rule: key < min(stride, count) takes the place of key < the
+ *   slots of ks.  d_gen_out is device memory like d_result: exactly report->n_selected elements are written.
+ *   The plan: ChaCha20-Poly1305 as in rx_open.  AES always takes the wave-per-record kernel (planned_on_device = 1,
+ *   lanes = 64), whatever the key runs say: the batch kernel's key-run chunks cannot carry a per-record key.  For bulk traffic
+ *   of one connection that is the slower record kernel: 262 144 packets of 1 350 bytes on one key take it 1.6 ms, the batch
+ *   kernel about 0.45 ms.  A receiver that wants the batch kernel's rate for such traffic uses rx_open with
+ *   the generation it knows.
+ *   PTLS_HIP_EINVAL, nothing launched, besides rx_open's refusals: a null kp, d_phase or d_gen_out; stride == 0 or
+ *   count == 0; 3 * stride above the slots of ks; rx_set_plan mode 2 (the host plan fixes a chunk's key on the host).
+ *   ks and hp_ks are in use until the launches are done, as for rx_open; the state array is read by the header kernel.
+ * rx_keyphase_commit: follows the rx_open_keyphase whose d_result, d_pn_out and d_gen_out it is given, on the same stream,
+ *   before the next open on the object (it reads the connection of selected packet j from the object's packed descriptors).
+ *   For every connection c < count, let N be its selected packets with d_result != UINT64_MAX and d_gen_out == gen + 1, and C
+ *   those with d_gen_out == gen.  N not empty: gen += 1, first_pn = min pn over N, and c is listed in d_updated.  Otherwise,
+ *   C not empty: first_pn = min(first_pn, min pn over C).  Otherwise the entry is unchanged.  Packets that failed
+ *   authentication, previous-generation packets and long-header packets change nothing: a forged packet with a flipped bit
+ *   does not advance a connection (RFC 9001 §6.3).  d_updated (device, room for `count` elements) receives the updated
+ *   connections in ascending order, *n_updated their number: the host then derives the keys of generation gen + 1 of exactly
+ *   those connections into the bank that generation gen - 2 has left (ptls_hip_keyset_update_quic_secrets).  It never reads a
+ *   result array.  The outcome does not depend on the order in which the packets are looked at.  One stream
+ *   synchronisation, to read the count.
+ *   PTLS_HIP_EINVAL, nothing launched: a null pointer; count == 0 or above 2^32 - 1; no rx_open_keyphase on the object since
+ *   its entries were loaded or since a plain rx_open.
+ * Out of scope: the key phase with the AES batch kernel (key-run chunks made on the device), with the QUIC batches of 2e and
+ * the host pipelines of 2g; an indexed update_quic_secrets (today: contiguous ranges); advancing d_expected_pn on the device;
+ * checking the reserved bits; the usage limits of RFC 9001 §6.6 and the handshake-confirmed rule of §6.2. */
+typedef struct st_ptls_hip_quic_rx_keyphase_t {
+    const ptls_hip_quic_keyphase_t *d_phase; /* device: the per-connection state */
+    size_t count;                            /* its entries */
+    size_t stride;                           /* the bank stride in ks */
+    uint32_t *d_gen_out;                     /* device: one generation per selected packet, like d_result */
+} ptls_hip_quic_rx_keyphase_t;
+int ptls_hip_quic_rx_open_keyphase(ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, uint32_t type_mask,
+                                   const ptls_hip_quic_rx_keyphase_t *kp, void *d_buf, size_t buf_len, void *d_out,
+                                   size_t out_len, uint32_t *d_sel, uint64_t *d_result, uint64_t *d_pn_out,
+                                   ptls_hip_quic_rx_report_t *report, void *stream);
+int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip_quic_keyphase_t *d_phase, size_t count,
+                                     const uint64_t *d_result, const uint64_t *d_pn_out, const uint32_t *d_gen_out,
+                                     uint32_t *d_updated, size_t *n_updated, void *stream);
+/* Diagnostic (tools/bench_quic_keyphase.py): with ptls_hip_quic_rx_timing enabled on the calling thread, the HIP-event times of
+ * the last rx_open_keyphase's header kernel and of the last rx_keyphase_commit's launches (either pointer may be NULL). */
+void ptls_hip_quic_rx_keyphase_timing(float *header_ms, float *commit_ms);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
