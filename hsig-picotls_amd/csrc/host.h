@@ -17,7 +17,8 @@
  *   quic_rx.cpp        the QUIC receive object: parsed entries kept on the device, selected, packed, planned and opened there
  *                      (kernels: quic_rx_kernel.hip; the select rule and the sums' terms shared with the CPU check: quic_rx.h),
  *                      and on it the key chosen by Key Phase bit and the commit of key updates (kernels:
- *                      quic_phase_kernel.hip; the rule shared with the CPU check: quic_phase.h)
+ *                      quic_phase_kernel.hip; the rule shared with the CPU check: quic_phase.h), and the received packet
+ *                      numbers tracked behind an open call (kernels: quic_track_kernel.hip; the rule: quic_track.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
  *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)

@@ -272,6 +272,41 @@ int launch_quic_phase_mark(const QuicCommitArgs &a, uint32_t m, unsigned grid, v
  * over the flags: the entry moved on by quic_phase_apply, mins reset, and an updated connection listed at its position */
 int launch_quic_phase_apply(const QuicCommitArgs &a, int place, unsigned grid, void *stream);
 
+/* ---- received packet numbers tracked on the device (quic_track_kernel.hip; the rule shared with the host and the CPU
+ * check: quic_track.h) ---- */
+
+struct QuicTrackArgs {
+    ptls_hip_quic_pnspace_t *spaces; /* 3 x count entries: read by the claim and verdict passes, rewritten by the apply pass */
+    uint32_t count;
+    uint32_t n;                            /* the loaded entries: sel[j] is looked at only when below it */
+    const ptls_hip_quic_packet_t *packed;  /* the selected packets' descriptors: key = the connection */
+    const ptls_hip_quic_pktinfo_t *info;   /* the loaded entries' info records: type, through sel */
+    const uint32_t *sel;
+    const uint64_t *result, *pn_out;
+    uint64_t *acc;        /* 2 x 3 x count: per space, [2 p] = 1 + the largest packet number of the call's candidates (0: none),
+                             [2 p + 1] = the window bits of its new packets; 0 between calls */
+    uint32_t *table;      /* `slots` positions, QTK_EMPTY before the claim pass */
+    uint64_t slots;
+    uint32_t *verdict;
+    uint64_t *expected_pn; /* or nullptr */
+    uint64_t expected_count;
+    uint32_t *l0;         /* the scan levels over the 0 / 1 "has a new packet" flags per connection, as in QuicCommitArgs */
+    const uint32_t *l1, *l2;
+    uint32_t *touched;    /* the connections with a new packet, ascending */
+};
+
+/* packets per thread of the claim pass, as QPH_MARK_PER_THREAD */
+constexpr uint32_t QTK_CLAIM_PER_THREAD = 4;
+/* a thread per QTK_CLAIM_PER_THREAD selected packets: a tracked packet that the old state does not refuse enters the table
+ * (32-bit CAS / atomicMin on positions) and raises its space's acc[2 p] (64-bit atomicMax, behind a per-lane fold and a
+ * per-wave reduction) */
+int launch_quic_track_claim(const QuicTrackArgs &a, uint32_t m, unsigned grid, void *stream);
+/* a thread per selected packet, after the claim pass: the verdict, and a new packet's window bit into acc[2 p + 1] */
+int launch_quic_track_verdict(const QuicTrackArgs &a, uint32_t m, unsigned grid, void *stream);
+/* one thread per connection.  place == 0: the flag "a space of c has a new packet" into l0.  place != 0, after the scans over
+ * the flags: each such space moved on by quic_track_apply, its expected_pn stored, acc reset, and c listed at its position */
+int launch_quic_track_apply(const QuicTrackArgs &a, int place, unsigned grid, void *stream);
+
 /* quic_slice_kernel.hip, behind launch_quic_unprotect on a copy-transport slice: 8 bytes per packet at packed + 8 t = the
  * count of unprotected header bytes (0 with PTLS_HIP_QUIC_UNPROTECTED, else 1 + pn_len), the first byte, the packet-number
  * bytes, read from the packets at pkt */

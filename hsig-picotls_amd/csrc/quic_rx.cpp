@@ -7,6 +7,8 @@
  * the host and through ptls_hip_quic_batch_new / ptls_hip_quic_open_batch as they are.
  * The same open call with the key chosen by Key Phase bit, and the commit of key updates (2j): the rule is
  * quic_phase.h's, the kernels quic_phase_kernel.hip's.
+ * And the received packet numbers tracked behind an open call (2k): the rule is quic_track.h's, the kernels
+ * quic_track_kernel.hip's.
  */
 #include <algorithm>
 #include <cstdio>
@@ -16,11 +18,12 @@
 
 #define GF128_FN static inline
 #include "quic_rx.h"
+#include "quic_track.h"
 
 namespace {
 
 thread_local bool g_timing = false;
-thread_local float g_select_ms = 0, g_plan_ms = 0, g_header_ms = 0, g_commit_ms = 0;
+thread_local float g_select_ms = 0, g_plan_ms = 0, g_header_ms = 0, g_commit_ms = 0, g_track_ms = 0;
 
 size_t sort_tiles(size_t m)
 {
@@ -56,7 +59,14 @@ struct st_ptls_hip_quic_rx_t {
     size_t kp_cap = 0;
     bool kp_open = false; /* the last open call was rx_open_keyphase: d_packed holds its kp_m selected packets */
     size_t kp_m = 0;
-    hipEvent_t ev[8] = {}; /* select 0-1, sort 2-3, header kernel 4-5, commit 6-7 */
+    /* the track call's scratch: per space the maximum and the window bits (tk_cap connections, 0 between calls), the scan
+     * levels, and the table of candidates (tk_slots positions) */
+    uint64_t *d_tk_acc = nullptr;
+    uint32_t *d_tk_levels = nullptr, *d_tk_table = nullptr;
+    size_t tk_cap = 0, tk_slots = 0;
+    bool opened = false; /* an open call has run since the entries were loaded: d_packed holds its open_m selected packets */
+    size_t open_m = 0;
+    hipEvent_t ev[10] = {}; /* select 0-1, sort 2-3, header kernel 4-5, commit 6-7, track 8-9 */
     Uses uses; /* the launches that read or write the arrays above: rx_free waits for them */
 
     template <class T>
@@ -109,7 +119,7 @@ extern "C" void ptls_hip_quic_rx_free(ptls_hip_quic_rx_t *rx)
         return;
     void *const mem[] = {rx->d_pkts,  rx->d_info,     rx->d_dgrams, rx->d_parse_levels, rx->d_sel_levels, rx->d_packed, rx->d_keys,
                          rx->d_recs,  rx->d_recs_ord, rx->d_order,  rx->d_order_tmp,    rx->d_hist,       rx->d_stats,  rx->d_chunk,
-                         rx->d_kp_mins, rx->d_kp_levels};
+                         rx->d_kp_mins, rx->d_kp_levels, rx->d_tk_acc, rx->d_tk_levels, rx->d_tk_table};
     bool any = false;
     for (void *p : mem)
         any = any || p != nullptr;
@@ -143,6 +153,7 @@ extern "C" int ptls_hip_quic_rx_parse(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
     rx->has_info = true;
     rx->order_n = 0;
     rx->kp_open = false;
+    rx->opened = false;
     *n_pkts = 0;
     if (n == 0)
         return 0;
@@ -188,6 +199,7 @@ extern "C" int ptls_hip_quic_rx_set_packets(ptls_hip_quic_rx_t *rx, const ptls_h
     rx->has_info = d_info != nullptr;
     rx->order_n = 0;
     rx->kp_open = false;
+    rx->opened = false;
     if (n == 0)
         return 0;
     DeviceGuard g(rx->eng->device);
@@ -303,6 +315,7 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
     report->planned_on_device = 0;
     report->lanes = 0;
     rx->kp_open = false;
+    rx->opened = false;
     if (rx->n == 0)
         return 0;
     if (d_buf == nullptr || d_out == nullptr || d_sel == nullptr || d_result == nullptr || d_pn_out == nullptr)
@@ -376,6 +389,8 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
     report->n_selected = m;
     rx->kp_open = kp != nullptr;
     rx->kp_m = m;
+    rx->opened = true;
+    rx->open_m = m;
     if (m == 0)
         return 0;
 
@@ -547,5 +562,108 @@ extern "C" int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip
     if (g_timing)
         g_commit_ms = rx->between(6, 7);
     *n_updated = total;
+    return 0;
+}
+
+extern "C" void ptls_hip_quic_rx_track_timing(float *track_ms)
+{
+    if (track_ms != nullptr)
+        *track_ms = g_track_ms;
+}
+
+extern "C" int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_rx_track_t *tr, const uint32_t *d_sel,
+                                      const uint64_t *d_result, const uint64_t *d_pn_out, size_t *n_touched, void *stream)
+{
+    const char *who = "quic_rx_track";
+    if (rx == nullptr || tr == nullptr || d_sel == nullptr || d_result == nullptr || d_pn_out == nullptr || n_touched == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null receive object, parameters, array or n_touched", who);
+    if (tr->d_spaces == nullptr || tr->d_verdict == nullptr || tr->d_touched == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null state, verdict or touched array", who);
+    if (tr->count == 0 || tr->count > 0xffffffffu)
+        return fail(PTLS_HIP_EINVAL, "%s: a connection count of %zu is outside 1 .. 2^32 - 1", who, tr->count);
+    if (tr->d_expected_pn == nullptr && tr->expected_count != 0)
+        return fail(PTLS_HIP_EINVAL, "%s: no expected-pn table, but %zu entries of it", who, tr->expected_count);
+    if (!rx->opened)
+        return fail(PTLS_HIP_EINVAL, "%s: no open call on the object since its entries were loaded", who);
+    if (!rx->has_info)
+        return fail(PTLS_HIP_EINVAL, "%s: the entries were loaded without info records: no packet-number space is known", who);
+    *n_touched = 0;
+    const size_t m = rx->open_m, count = tr->count;
+    if (m == 0)
+        return 0; /* nothing was selected: no entry changes */
+
+    ptls_hip_engine_t *eng = rx->eng;
+    DeviceGuard g(eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (count > rx->tk_cap) { /* (grown: the launches that used the smaller arrays are waited for first) */
+        if (rx->d_tk_acc != nullptr || rx->d_tk_levels != nullptr) {
+            rx->uses.wait();
+            dev_free(eng, rx->d_tk_acc);
+            dev_free(eng, rx->d_tk_levels);
+            rx->d_tk_acc = nullptr, rx->d_tk_levels = nullptr, rx->tk_cap = 0;
+        }
+        int e = rx->ensure(&rx->d_tk_acc, 6 * count * sizeof(uint64_t));
+        if (e == 0)
+            e = rx->ensure(&rx->d_tk_levels, scan_levels(nullptr, count).words * sizeof(uint32_t));
+        if (e != 0)
+            return e;
+        HIP_TRY(hipMemsetAsync(rx->d_tk_acc, 0, 6 * count * sizeof(uint64_t), s), PTLS_HIP_ENODEV); /* once */
+        rx->tk_cap = count;
+    }
+    const uint64_t slots = quic_track_slots(m);
+    if (slots > rx->tk_slots) {
+        if (rx->d_tk_table != nullptr) {
+            rx->uses.wait();
+            dev_free(eng, rx->d_tk_table);
+            rx->d_tk_table = nullptr, rx->tk_slots = 0;
+        }
+        if (int e = rx->ensure(&rx->d_tk_table, slots * sizeof(uint32_t)))
+            return e;
+        rx->tk_slots = slots;
+    }
+    const ScanLevels L = scan_levels(rx->d_tk_levels, count);
+    QuicTrackArgs a{};
+    a.spaces = tr->d_spaces;
+    a.count = (uint32_t)count;
+    a.n = (uint32_t)rx->n;
+    a.packed = rx->d_packed;
+    a.info = rx->d_info;
+    a.sel = d_sel;
+    a.result = d_result;
+    a.pn_out = d_pn_out;
+    a.acc = rx->d_tk_acc;
+    a.table = rx->d_tk_table;
+    a.slots = slots;
+    a.verdict = tr->d_verdict;
+    a.expected_pn = tr->d_expected_pn;
+    a.expected_count = tr->expected_count;
+    a.l0 = L.l0;
+    a.l1 = L.has1 ? L.l1 : nullptr;
+    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.touched = tr->d_touched;
+    const unsigned claim_grid = quic_scan_grid((m + 256 * QTK_CLAIM_PER_THREAD - 1) / (256 * QTK_CLAIM_PER_THREAD), eng->ncu);
+    const unsigned pkt_grid = quic_scan_grid((m + 255) / 256, eng->ncu);
+    const unsigned conn_grid = quic_scan_grid((count + 255) / 256, eng->ncu);
+    rx->mark(8, s);
+    HIP_TRY(hipMemsetAsync(rx->d_tk_table, 0xff, slots * sizeof(uint32_t), s), PTLS_HIP_ENODEV); /* every slot QTK_EMPTY */
+    int e = launch_quic_track_claim(a, (uint32_t)m, claim_grid, stream);
+    if (e == 0)
+        e = launch_quic_track_verdict(a, (uint32_t)m, pkt_grid, stream);
+    if (e == 0)
+        e = launch_quic_track_apply(a, 0, conn_grid, stream);
+    if (e == 0)
+        e = launch_scan_levels(L, eng->ncu, stream);
+    if (e == 0)
+        e = launch_quic_track_apply(a, 1, conn_grid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    rx->uses.note(stream);
+    rx->mark(9, s);
+    uint32_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, L.total, sizeof(total), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
+    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    if (g_timing)
+        g_track_ms = rx->between(8, 9);
+    *n_touched = total;
     return 0;
 }

@@ -52,6 +52,10 @@ QUIC_NO_CONN = 0xFFFFFFFF
 QUIC_KEYPHASE_DTYPE = np.dtype([("first_pn", "<u8"), ("gen", "<u4"), ("reserved", "<u4")])
 assert QUIC_KEYPHASE_DTYPE.itemsize == 16
 QUIC_NO_GEN = 0xFFFFFFFF
+# ptls_hip_quic_pnspace_t: the received packet numbers of connection c, space s at [3 c + s] (Initial 0, Handshake 1, 0/1-RTT 2)
+QUIC_PNSPACE_DTYPE = np.dtype([("next", "<u8"), ("window", "<u8")])
+assert QUIC_PNSPACE_DTYPE.itemsize == 16
+QUIC_PN_NONE, QUIC_PN_NEW, QUIC_PN_DUPLICATE, QUIC_PN_TOO_OLD = range(4)
 EINVAL = -1
 
 
@@ -132,6 +136,9 @@ SIGNATURES = {
     "ptls_hip_quic_rx_keyphase_commit": (_i, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, ctypes.POINTER(_sz), _vp]),
     # diagnostic only (tools/bench_quic_keyphase.py): HIP-event times of the last header kernel and commit
     "ptls_hip_quic_rx_keyphase_timing": (None, [ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
+    "ptls_hip_quic_rx_track": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_sz), _vp]),
+    # diagnostic only (tools/bench_quic_track.py): HIP-event time of the last track call's launches
+    "ptls_hip_quic_rx_track_timing": (None, [ctypes.POINTER(ctypes.c_float)]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -578,6 +585,12 @@ class QuicRxKeyphase(ctypes.Structure):
     _fields_ = [("d_phase", ctypes.c_void_p), ("count", ctypes.c_size_t), ("stride", ctypes.c_size_t), ("d_gen_out", ctypes.c_void_p)]
 
 
+class QuicRxTrack(ctypes.Structure):
+    """ptls_hip_quic_rx_track_t"""
+    _fields_ = [("d_spaces", ctypes.c_void_p), ("count", ctypes.c_size_t), ("d_expected_pn", ctypes.c_void_p),
+                ("expected_count", ctypes.c_size_t), ("d_verdict", ctypes.c_void_p), ("d_touched", ctypes.c_void_p)]
+
+
 class QuicRx:
     """the receive object (ptls_hip_quic_rx_*): parsed entries stay on the device; open() selects, packs, plans and opens
     them there.  Calls on one QuicRx must be ordered (same stream)."""
@@ -664,6 +677,20 @@ class QuicRx:
         n = ctypes.c_size_t(0)
         _check(lib().ptls_hip_quic_rx_keyphase_commit(self.ptr, _ptr(d_phase), count, _ptr(d_result), _ptr(d_pn_out), _ptr(d_gen_out),
                                                       _ptr(d_updated), ctypes.byref(n), _stream(stream)), "quic_rx_keyphase_commit")
+        return n.value
+
+    def track(self, d_spaces, count, d_sel, d_result, d_pn_out, d_verdict, d_touched, d_expected_pn=None, expected_count=None,
+              stream=None):
+        """after open() or open_keyphase() with the same d_sel, d_result and d_pn_out: d_verdict[j] = QUIC_PN_* of selected
+        packet j against d_spaces (device, 3 * count QUIC_PNSPACE_DTYPE entries), which moves on; d_expected_pn[3 c + s] (device,
+        uint64, or None) = the new `next` of every space with a new packet; the connections with a new packet go to d_touched
+        (device, uint32, ascending); returns their number"""
+        if expected_count is None:
+            expected_count = d_expected_pn.numel() if d_expected_pn is not None else 0
+        n, tr = ctypes.c_size_t(0), QuicRxTrack(_ptr(d_spaces), count, _ptr(d_expected_pn), expected_count, _ptr(d_verdict),
+                                                _ptr(d_touched))
+        _check(lib().ptls_hip_quic_rx_track(self.ptr, ctypes.addressof(tr), _ptr(d_sel), _ptr(d_result), _ptr(d_pn_out),
+                                            ctypes.byref(n), _stream(stream)), "quic_rx_track")
         return n.value
 
     def close(self):

@@ -860,8 +860,7 @@ typedef struct st_ptls_hip_quic_keyphase_t {
  *   PTLS_HIP_EINVAL, nothing launched: a null pointer; count == 0 or above 2^32 - 1; no rx_open_keyphase on the object since
  *   its entries were loaded or since a plain rx_open.
  * Out of scope: the key phase with the AES batch kernel (key-run chunks made on the device), with the QUIC batches of 2e and
- * the host pipelines of 2g; an indexed update_quic_secrets (today: contiguous ranges); advancing d_expected_pn on the device;
- * checking the reserved bits; the usage limits of RFC 9001 §6.6 and the handshake-confirmed rule of §6.2. */
+ * the host pipelines of 2g; an indexed update_quic_secrets (today: contiguous ranges); checking the reserved bits; the usage limits of RFC 9001 §6.6 and the handshake-confirmed rule of §6.2. */
 typedef struct st_ptls_hip_quic_rx_keyphase_t {
     const ptls_hip_quic_keyphase_t *d_phase; /* device: the per-connection state */
     size_t count;                            /* its entries */
@@ -878,6 +877,69 @@ int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip_quic_keyph
 /* Diagnostic (tools/bench_quic_keyphase.py): with ptls_hip_quic_rx_timing enabled on the calling thread, the HIP-event times of
  * the last rx_open_keyphase's header kernel and of the last rx_keyphase_commit's launches (either pointer may be NULL). */
 void ptls_hip_quic_rx_keyphase_timing(float *header_ms, float *commit_ms);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2k. received packet numbers tracked on the device: replays, and the expected packet number     *
+ *     (RFC 9000 §12.3, §13.2.3, §17.1)                                                           *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The parse call decodes a truncated packet number against d_expected_pn[3 c + s], and a receiver must discard a packet
+ * unless it is certain that it has not processed one with the same number in that space (RFC 9000 §12.3).  rx_track settles
+ * both from the authenticated results of an open call, on the device: it keeps, per connection and packet-number space, the
+ * largest number accepted and a 64-packet window of accepted numbers, gives every selected packet a verdict, advances the
+ * table that the next parse call reads, and lists the connections that received something new.  The host reads one count and
+ * never a result array.  Like the key-phase commit, forged packets change nothing.
+ *
+ * The state is a caller-owned DEVICE array of 16-byte entries; entry [3 c + s] is for connection c (the value the parse call
+ * writes into `key`) and space s: Initial 0, Handshake 1, 0-RTT and 1-RTT 2. */
+typedef struct st_ptls_hip_quic_pnspace_t {
+    uint64_t next;   /* largest accepted packet number + 1; 0: none yet */
+    uint64_t window; /* bit k (k < 64): packet number next - 1 - k has been accepted; 0 when next == 0 */
+} ptls_hip_quic_pnspace_t;
+#define PTLS_HIP_QUIC_PN_NONE 0u      /* failed authentication, or not tracked: changes nothing */
+#define PTLS_HIP_QUIC_PN_NEW 1u
+#define PTLS_HIP_QUIC_PN_DUPLICATE 2u
+#define PTLS_HIP_QUIC_PN_TOO_OLD 3u   /* more than 64 behind the largest: cannot be proven new, discard */
+
+/* rx_track: follows an rx_open or rx_open_keyphase on the same stream, with that call's d_sel, d_result and d_pn_out, before
+ *   the next open or load on the object (it reads the connection of selected packet j from the object's packed descriptors
+ *   and its type from the object's info records through d_sel).  It may come before or after rx_keyphase_commit: neither reads
+ *   what the other writes.
+ *   Selected packet j is tracked if d_result[j] != UINT64_MAX, its connection is below `count` and its type is Initial,
+ *   0-RTT, Handshake or 1-RTT.  Every other packet gets PN_NONE and touches no state: a forged packet with a huge decoded
+ *   number advances nothing.  A tracked packet with pn = d_pn_out[j], in a space whose state BEFORE the call is (next, window):
+ *     1. pn < next and next - 1 - pn >= 64: PN_TOO_OLD.
+ *     2. pn < next and bit next - 1 - pn of window set: PN_DUPLICATE.
+ *     3. otherwise, a tracked packet j' < j of the same space has the same pn: PN_DUPLICATE (the lowest position wins).
+ *     4. otherwise PN_NEW.
+ *   Rule 1 looks at the state before the call: a bulk batch of fresh packets of one connection is all PN_NEW.
+ *   After the call, next' = max(next, 1 + the largest pn among the NEW packets) and window' = window << (next' - next) (0 for
+ *   a shift of 64 or more) OR bit next' - 1 - pn of every NEW packet with next' - 1 - pn < 64.  NEW packets further back are
+ *   accepted and not remembered: a later replay of one is PN_TOO_OLD, so nothing behind the window is accepted twice.  A space
+ *   without a NEW packet keeps its 16 bytes.  The outcome does not depend on the order in which the packets are looked at.
+ *   Exactly n_selected elements of d_verdict are written.  d_expected_pn[3 c + s] = next' is written for every space with a
+ *   NEW packet and 3 c + s < expected_count, and no other element.  d_touched receives the connections with at least one NEW
+ *   packet in ascending order, *n_touched their number; exactly that many elements are written.  One stream
+ *   synchronisation, to read the count.  Nothing selected: 0 with *n_touched = 0 and nothing written.
+ *   PTLS_HIP_EINVAL, nothing launched: a null object, struct, d_spaces, d_verdict, d_touched, d_sel, d_result, d_pn_out or
+ *   n_touched; count == 0 or above 2^32 - 1; d_expected_pn == NULL with expected_count != 0; no open on the object since its
+ *   entries were loaded; entries loaded without info records (rx_set_packets with d_info == NULL).
+ *   The call's scratch belongs to the object: allocated with the first use, grown when a call needs more, released by rx_free.
+ * Out of scope: windows wider than 64; ACK frames and ACK ranges (the host reads the state entries of the listed
+ * connections); the batches of 2e, the pipelines of 2g and the node API; discarding packet-number spaces; ECN counts. */
+typedef struct st_ptls_hip_quic_rx_track_t {
+    ptls_hip_quic_pnspace_t *d_spaces; /* device: 3 * count entries */
+    size_t count;                      /* connections */
+    uint64_t *d_expected_pn;           /* device, or NULL: the table the parse call reads */
+    size_t expected_count;             /* its entries */
+    uint32_t *d_verdict;               /* device: one per selected packet, like d_result */
+    uint32_t *d_touched;               /* device, room for count: connections with at least one NEW packet, ascending */
+} ptls_hip_quic_rx_track_t;
+int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_rx_track_t *tr, const uint32_t *d_sel,
+                           const uint64_t *d_result, const uint64_t *d_pn_out, size_t *n_touched, void *stream);
+/* Diagnostic (tools/bench_quic_track.py): with ptls_hip_quic_rx_timing enabled on the calling thread, the HIP-event time of the
+ * last rx_track's launches (the pointer may be NULL). */
+void ptls_hip_quic_rx_track_timing(float *track_ms);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
