@@ -19,6 +19,9 @@
  *                      and on it the key chosen by Key Phase bit and the commit of key updates (kernels:
  *                      quic_phase_kernel.hip; the rule shared with the CPU check: quic_phase.h), and the received packet
  *                      numbers tracked behind an open call (kernels: quic_track_kernel.hip; the rule: quic_track.h)
+ *   quic_tx.cpp        the QUIC send object: requests in device memory numbered, given headers and a key generation from a
+ *                      per-connection state table on the device, compacted, planned and sealed there (kernels:
+ *                      quic_tx_kernel.hip; the rule shared with the CPU check: quic_tx.h)
  *   tls13.cpp          the TLS 1.3 record layer over the batch (framing, parsing)
  *   slice_plan.cpp     the copy transport's planning: a slice's cut, descriptors, copies back, gaps, mask places, and for
  *                      QUIC packets the headers and plaintext tails staged with the gaps (no HIP call)

@@ -374,6 +374,48 @@ int launch_quic_rx_hist(const uint32_t *keys, const uint32_t *src, uint32_t m, u
 int launch_quic_rx_scatter(const uint32_t *keys, const uint32_t *src, uint32_t m, uint32_t shift, const uint32_t *hl0,
                            const uint32_t *hl1, const uint32_t *hl2, uint32_t *dst, void *stream);
 
+/* ---- the send object (quic_tx_kernel.hip; the rule shared with the host and the CPU check: quic_tx.h) ---- */
+
+struct QuicTxLimits; /* quic_tx.h */
+
+struct QuicTxArgs {
+    ptls_hip_quic_txconn_t *conns;             /* read by every pass in front of the apply pass, which alone writes it */
+    const ptls_hip_quic_keyphase_t *rx_phase;  /* or nullptr */
+    const ptls_hip_quic_txreq_t *reqs;
+    uint32_t n;
+    uint32_t *first;      /* per connection below the limits' nconn: the position of its first run's head; QTX_NO_POS between calls */
+    /* the scan levels over the run-head flags (r*: a head's exclusive prefix is its run's index) and over the sent flags (s*) */
+    uint32_t *r0;
+    const uint32_t *r1, *r2, *nruns;
+    uint32_t *s0;
+    const uint32_t *s1, *s2;
+    uint32_t *run_start;  /* run r begins at position run_start[r]; run_start[*nruns] = n */
+    uint32_t *status;     /* the caller's three output arrays */
+    uint64_t *pn_out;
+    uint32_t *pkt_len;
+    uint8_t *pkt;         /* the packet buffer: the build pass writes the headers of sent packets */
+    ptls_hip_quic_packet_t *packed; /* build: per sent packet, at its compacted position */
+    ptls_hip_record_t *recs;
+    ptls_hip_supp_t *supp;
+    uint32_t *keys;       /* its sort key (quic_tx_sort_key) */
+    uint64_t *stats;      /* QTX_NSTATS sums over the sent packets: zeroed by the head pass, summed by the select pass */
+};
+
+/* one thread per request: the run-head flag into r0; a head lowers first[conn] to its position (32-bit atomicMin) */
+int launch_quic_tx_heads(const QuicTxArgs &a, const QuicTxLimits &lim, unsigned grid, void *stream);
+/* after the scans over r0: a head stores its position at its run's index */
+int launch_quic_tx_runs(const QuicTxArgs &a, unsigned grid, void *stream);
+/* the rule per request: status, pn_out, pkt_len, the sent flag into s0, the sums */
+int launch_quic_tx_select(const QuicTxArgs &a, const QuicTxLimits &lim, unsigned grid, void *stream);
+/* after the scans over s0: a sent packet's header bytes, descriptors and sort key at its compacted position */
+int launch_quic_tx_build(const QuicTxArgs &a, const QuicTxLimits &lim, unsigned grid, void *stream);
+/* a launch of its own behind every pass that reads the state: the heads of numbered runs move their connection on and reset
+ * first[conn] */
+int launch_quic_tx_apply(const QuicTxArgs &a, const QuicTxLimits &lim, unsigned grid, void *stream);
+/* the wave-per-record kernel's view: recs_ord[t] = recs[order[t]] for t < m, and its single chunk {0, m, 0xffffffff, 0} */
+int launch_quic_tx_order(const ptls_hip_record_t *recs, const uint32_t *order, uint32_t m, ptls_hip_record_t *recs_ord, Chunk *chunk,
+                         unsigned grid, void *stream);
+
 /* ---- QUIC key derivation (quic_keys.hip; the arithmetic shared with the CPU check: quic_keys.h) ---- */
 
 /* the HMAC-SHA256 pad states of the Initial salt (quic_keys.h HkPads<HkSha256>), hashed on the host once per call */

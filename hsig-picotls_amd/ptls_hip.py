@@ -56,6 +56,13 @@ QUIC_NO_GEN = 0xFFFFFFFF
 QUIC_PNSPACE_DTYPE = np.dtype([("next", "<u8"), ("window", "<u8")])
 assert QUIC_PNSPACE_DTYPE.itemsize == 16
 QUIC_PN_NONE, QUIC_PN_NEW, QUIC_PN_DUPLICATE, QUIC_PN_TOO_OLD = range(4)
+# ptls_hip_quic_txconn_t / ptls_hip_quic_txreq_t: a connection's send state and one send request (the send object, QuicTx)
+QUIC_TXCONN_DTYPE = np.dtype([("next_pn", "<u8"), ("largest_acked", "<u8"), ("gen", "<u4"), ("dcid_len", "u1"), ("flags", "u1"),
+                              ("reserved", "u1", (2,)), ("dcid", "u1", (20,)), ("reserved2", "u1", (4,))])
+assert QUIC_TXCONN_DTYPE.itemsize == 48
+QUIC_TXREQ_DTYPE = np.dtype([("data_off", "<u8"), ("pkt_off", "<u8"), ("conn", "<u4"), ("len", "<u4")])
+assert QUIC_TXREQ_DTYPE.itemsize == 24
+QUIC_TX_SENT, QUIC_TX_NO_CONN, QUIC_TX_SPLIT, QUIC_TX_PN, QUIC_TX_RANGE = range(5)
 EINVAL = -1
 
 
@@ -139,6 +146,13 @@ SIGNATURES = {
     "ptls_hip_quic_rx_track": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_sz), _vp]),
     # diagnostic only (tools/bench_quic_track.py): HIP-event time of the last track call's launches
     "ptls_hip_quic_rx_track_timing": (None, [ctypes.POINTER(ctypes.c_float)]),
+    "ptls_hip_quic_tx_new": (_vp, [_vp, _sz]),
+    "ptls_hip_quic_tx_free": (None, [_vp]),
+    "ptls_hip_quic_tx_seal": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "ptls_hip_quic_tx_packets": (_vp, [_vp]),
+    "ptls_hip_quic_tx_count": (_sz, [_vp]),
+    # diagnostic only (tools/bench_quic_tx.py): HIP-event times of the last tx_seal's front passes and sort
+    "ptls_hip_quic_tx_timing": (None, [_i, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float)]),
     "ptls_hip_fill_records": (_i, [_vp, _vp, _u64, _u64, _vp, _vp]),
     "ptls_hip_device_copy": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ptls_hip_tls13_wire_size": (_sz, [_sz]),
@@ -696,6 +710,59 @@ class QuicRx:
     def close(self):
         if self.ptr:
             lib().ptls_hip_quic_rx_free(self.ptr)
+            self.ptr = None
+
+
+class QuicTxParams(ctypes.Structure):
+    """ptls_hip_quic_tx_params_t"""
+    _fields_ = [("d_conns", ctypes.c_void_p), ("count", ctypes.c_size_t), ("stride", ctypes.c_size_t), ("d_rx_phase", ctypes.c_void_p),
+                ("pn_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("d_status", ctypes.c_void_p), ("d_pn_out", ctypes.c_void_p),
+                ("d_pkt_len", ctypes.c_void_p)]
+
+
+class QuicTxReport(ctypes.Structure):
+    """ptls_hip_quic_tx_report_t"""
+    _fields_ = [("n_sent", ctypes.c_uint64), ("bytes", ctypes.c_uint64), ("lanes", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class QuicTx:
+    """the send object (ptls_hip_quic_tx_*): requests (QUIC_TXREQ_DTYPE, device) become protected short-header packets; the
+    packet numbers, the headers and the key generation come from d_conns (QUIC_TXCONN_DTYPE, device), which moves on.  Calls on
+    one QuicTx must be ordered (same stream)."""
+
+    def __init__(self, engine, cap):
+        self.engine, self.cap = engine, cap
+        self.ptr = lib().ptls_hip_quic_tx_new(engine.ptr, cap)
+        if not self.ptr:
+            raise HipError(f"ptls_hip_quic_tx_new: {last_error()}")
+
+    def __len__(self):
+        return lib().ptls_hip_quic_tx_count(self.ptr)
+
+    def seal(self, keyset, hp_keyset, d_conns, count, stride, d_reqs, n, d_in, in_len, d_pkt, buf_len, d_status, d_pn_out, d_pkt_len,
+             d_rx_phase=None, pn_len=0, stream=None):
+        """numbers, builds, seals and header-protects the n requests; d_status[j] = QUIC_TX_*, d_pn_out[j] and d_pkt_len[j] as
+        include/ptls_hip.h 2l defines them; returns the QuicTxReport (n_sent, bytes, lanes)"""
+        rep = QuicTxReport()
+        pr = QuicTxParams(_ptr(d_conns), count, stride, _ptr(d_rx_phase), pn_len, 0, _ptr(d_status), _ptr(d_pn_out), _ptr(d_pkt_len))
+        _check(lib().ptls_hip_quic_tx_seal(self.ptr, keyset.ptr, hp_keyset.ptr, ctypes.addressof(pr), _ptr(d_reqs), n, _ptr(d_in), in_len,
+                                           _ptr(d_pkt), buf_len, ctypes.addressof(rep), _stream(stream)), "quic_tx_seal")
+        return rep
+
+    def packets(self):
+        """the packed descriptors of the last call's sent packets, read back (tests)"""
+        import torch
+        n = len(self)
+        if n == 0:
+            return np.zeros(0, dtype=QUIC_PACKET_DTYPE)
+        nbytes = (n * QUIC_PACKET_DTYPE.itemsize + 15) & ~15
+        dev = torch.empty(nbytes, dtype=torch.uint8, device=f"cuda:{self.engine.device}")
+        self.engine.copy(dev, lib().ptls_hip_quic_tx_packets(self.ptr), nbytes)
+        return dev.cpu().numpy()[:n * QUIC_PACKET_DTYPE.itemsize].view(QUIC_PACKET_DTYPE).copy()
+
+    def close(self):
+        if self.ptr:
+            lib().ptls_hip_quic_tx_free(self.ptr)
             self.ptr = None
 
 

@@ -516,8 +516,8 @@ ptls_hip_batch_t *ptls_hip_quic_batch_records(ptls_hip_quic_batch_t *batch);
  * packets, the long-header fields up to pn_offset and pkt_len, and the key slot from the Destination Connection ID.
  * Out of scope: the node API (2d); handling Retry and Version Negotiation packets (they carry no packet protection; 2h
  * reports them and the host answers); choosing the key by key phase in these batches (the AES planner needs every packet's
- * key slot on the host; 2i plans on the device where the kernel's plan does not depend on the keys, and 2j chooses the key by
- * Key Phase bit there). */
+ * key slot on the host; 2i plans on the device where the kernel's plan does not depend on the keys, 2j chooses the receive key
+ * by Key Phase bit there, and 2l the send key, with the packet numbers and the headers). */
 int ptls_hip_quic_seal_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, const void *in,
                              void *pkt, void *stream);
 int ptls_hip_quic_open_batch(ptls_hip_quic_batch_t *batch, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks, void *pkt, void *out,
@@ -860,7 +860,7 @@ typedef struct st_ptls_hip_quic_keyphase_t {
  *   PTLS_HIP_EINVAL, nothing launched: a null pointer; count == 0 or above 2^32 - 1; no rx_open_keyphase on the object since
  *   its entries were loaded or since a plain rx_open.
  * Out of scope: the key phase with the AES batch kernel (key-run chunks made on the device), with the QUIC batches of 2e and
- * the host pipelines of 2g; an indexed update_quic_secrets (today: contiguous ranges); checking the reserved bits; the usage limits of RFC 9001 §6.6 and the handshake-confirmed rule of §6.2. */
+ * the host pipelines of 2g (the send side follows a committed update in 2l); an indexed update_quic_secrets (today: contiguous ranges); checking the reserved bits; the usage limits of RFC 9001 §6.6 and the handshake-confirmed rule of §6.2. */
 typedef struct st_ptls_hip_quic_rx_keyphase_t {
     const ptls_hip_quic_keyphase_t *d_phase; /* device: the per-connection state */
     size_t count;                            /* its entries */
@@ -940,6 +940,118 @@ int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_rx_track_
 /* Diagnostic (tools/bench_quic_track.py): with ptls_hip_quic_rx_timing enabled on the calling thread, the HIP-event time of the
  * last rx_track's launches (the pointer may be NULL). */
 void ptls_hip_quic_rx_track_timing(float *track_ms);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2l. the send object: packet numbers assigned, headers written and send keys chosen on the     *
+ *     device (RFC 9000 §12.3, §17.1, §17.3.1, A.2; RFC 9001 §6.2)                                 *
+ * ------------------------------------------------------------------------------------------ */
+
+/* The mirror of the receive object for short-header (1-RTT) packets.  With 2e the host chooses every packet number and its
+ * encoded length, writes the header bytes, knows the current key generation, fills and uploads a 40-byte descriptor per packet
+ * and plans on the host.  Here the host hands over "connection c, payload at this offset, this many bytes, put the packet
+ * there" as a DEVICE array of requests, and the device does the rest from a per-connection state table that it keeps up to
+ * date: a call reads one count and two sums back.
+ *
+ * Both arrays are caller-owned DEVICE memory; entry c of the state table is connection c. */
+typedef struct st_ptls_hip_quic_txconn_t { /* 48 bytes */
+    uint64_t next_pn;        /* the next packet number to assign */
+    uint64_t largest_acked;  /* largest packet number the peer has acknowledged; UINT64_MAX: none yet */
+    uint32_t gen;            /* generation of the send keys (<= 2^32 - 2); Key Phase bit = gen & 1 */
+    uint8_t dcid_len;        /* 0..20 */
+    uint8_t flags;           /* bit 0: the spin bit to send; other bits 0 */
+    uint8_t reserved[2];
+    uint8_t dcid[20];
+    uint8_t reserved2[4];
+} ptls_hip_quic_txconn_t;
+typedef struct st_ptls_hip_quic_txreq_t { /* 24 bytes */
+    uint64_t data_off;  /* the plaintext payload in d_in */
+    uint64_t pkt_off;   /* where the packet's first byte goes in d_pkt */
+    uint32_t conn;
+    uint32_t len;       /* payload bytes */
+} ptls_hip_quic_txreq_t;
+#define PTLS_HIP_QUIC_TX_SENT 0u
+#define PTLS_HIP_QUIC_TX_NO_CONN 1u /* conn outside the state table, the key banks or the header-protection keyset */
+#define PTLS_HIP_QUIC_TX_SPLIT 2u   /* a later run of a connection whose first run the call numbered */
+#define PTLS_HIP_QUIC_TX_PN 3u      /* no packet number or no encodable length for it */
+#define PTLS_HIP_QUIC_TX_RANGE 4u   /* the connection ID, the packet or the payload does not fit */
+
+/* Keys are laid out as in 2j: the AEAD keys of generation g of connection c sit in slot c + stride * (g % 3) of ks, the
+ * header-protection key in slot c of hp_ks; the host derives each next generation's send keys ahead of time into the free
+ * bank, as for receive.  With d_rx_phase (2j's state array, `count` entries) the generation used for connection c is
+ * max(txconn.gen, d_rx_phase[c].gen), and that value is stored back into txconn.gen: the sender follows a peer's key update
+ * that rx_keyphase_commit committed (RFC 9001 §6.2) with no host step.
+ *
+ * The rule, over the n requests of a call; every value of the state table is the one BEFORE the call:
+ *   1. A run is a maximal stretch of consecutive requests with the same conn.  A connection's packets in one call must form
+ *      one run: its first run by position is numbered, every later run of it gets TX_SPLIT and touches nothing.
+ *   2. TX_NO_CONN if conn >= min(count, stride, slots of hp_ks).
+ *   3. Request j of a numbered run that starts at position h gets pn = next_pn + (j - h) (the sum saturates at 2^64 - 1).
+ *      Requests refused under 4 and 5 still consume their number: gaps are legal (RFC 9000 §12.3).
+ *   4. TX_PN if pn >= 2^62, or largest_acked != UINT64_MAX and largest_acked >= pn, or no allowed length suffices: with
+ *      num_unacked = largest_acked == UINT64_MAX ? pn + 1 : pn - largest_acked, pn_len is the smallest L in
+ *      max(1, params.pn_len) .. 4 with num_unacked < 2^(8 L - 1) (RFC 9000 §17.1: more than twice the range; A.2).
+ *   5. TX_RANGE for dcid_len > 20, pn_len + len < 4 (the header-protection sample would leave the packet),
+ *      pkt_len = 1 + dcid_len + pn_len + len + 16 > 65535, data_off + len > in_len, or pkt_off + pkt_len > buf_len; none of
+ *      these sums wraps.
+ *   6. Otherwise TX_SENT: the header 0x40 | spin << 5 | (gen & 1) << 2 | (pn_len - 1), the DCID, the low pn_len bytes of pn
+ *      big-endian is written at d_pkt + pkt_off, and the packet is sealed under slot conn + stride * (gen % 3) and
+ *      header-protected exactly as ptls_hip_quic_seal_batch would for that header.
+ *   The precedence is NO_CONN, SPLIT, PN, RANGE.
+ * After the call, for every connection with a numbered run: next_pn += the run's length (saturating), gen = the generation
+ * used; every other byte of the table is unchanged.  d_status[j]; d_pn_out[j] = the number, or UINT64_MAX for NO_CONN and
+ * SPLIT; d_pkt_len[j] = 0 unless SENT: exactly n elements of each are written.  In d_pkt exactly the pkt_len bytes of sent
+ * packets change; d_in is not written.  Packet areas must be pairwise disjoint (the caller's duty, as in 2e).  The outcome does
+ * not depend on the order in which the requests are looked at.
+ *
+ * tx_new: room for cap requests per call; the scratch is the object's, allocated with the first use of each array and kept:
+ *   a steady-state call allocates nothing.  NULL for a null engine or cap outside 1 .. 2^32 - 1.  tx_free waits for the
+ *   launches that used the object.
+ * tx_seal: report->n_sent, ->bytes (the sum of pkt_len) and ->lanes (the lanes per record of the launch).  It synchronises
+ *   `stream` once, to read its sums, and returns with the record and header kernels in flight.  n == 0 returns 0.
+ *   ChaCha20-Poly1305 goes on its kernel with lanes from the sums.  AES always takes the wave-per-record kernel (lanes = 64)
+ *   behind a stable sort by block count, as rx_open_keyphase does and for 2j's reason: the batch kernel's key-run chunks, planned
+ *   on the host, cannot carry a per-record key.  2j measured that kernel at 1.6 ms against the batch kernel's 0.45 ms for 262 144
+ *   packets of 1 350 bytes on one key; that is the known price here for bulk traffic of one connection, and a sender that wants
+ *   the batch kernel's rate for such traffic uses 2e.  On the send side that batch measured 2.0 ms for this call against 0.5 ms for a planned
+ *   2e batch's seal, and 9.9 ms for the 2e path with its host steps.
+ *   PTLS_HIP_EINVAL, nothing launched and no byte touched: a null object, keyset, params, report, state, output array, or with
+ *   n != 0 a null request array or buffer; n above cap; count == 0 or above 2^32 - 1; stride == 0; 3 * stride above the slots
+ *   of ks; pn_len above 4 or a non-zero params.reserved; keysets of another engine than the object's, or of different algorithms or key sizes;
+ *   [d_in, in_len) overlapping [d_pkt, buf_len).
+ *   Ordering: calls on one send object, and calls that write its state table, must be ordered by the caller (same stream).
+ * tx_packets / tx_count: the packed 40-byte descriptors (2e's) of the last call's sent packets, in request order (a device
+ *   pointer, NULL when none), and their number.
+ * tx_timing: diagnostic (tools/bench_quic_tx.py), as rx_timing: with it enabled on the calling thread, the HIP-event times of
+ *   the last tx_seal's launches in front of the record kernel (numbering, select, build, state) and of its sort launches.
+ * Out of scope: long headers; coalescing; padding; frame building; in-place payloads (d_in inside d_pkt); the host pipelines
+ * (2g) and the node API (2d); the AEAD usage limits of RFC 9001 §6.6; the host plan (key-run chunks for the AES batch
+ * kernel). */
+typedef struct st_ptls_hip_quic_tx_t ptls_hip_quic_tx_t;
+typedef struct st_ptls_hip_quic_tx_params_t {
+    ptls_hip_quic_txconn_t *d_conns;           /* device: the per-connection send state */
+    size_t count;                              /* its entries */
+    size_t stride;                             /* the bank stride in ks */
+    const ptls_hip_quic_keyphase_t *d_rx_phase; /* device, or NULL: 2j's receive state, `count` entries */
+    uint32_t pn_len;                           /* 0: minimal; 1..4: at least that many packet-number bytes */
+    uint32_t reserved;                         /* 0 */
+    uint32_t *d_status;                        /* device: one PTLS_HIP_QUIC_TX_* per request */
+    uint64_t *d_pn_out;                        /* device: one per request */
+    uint32_t *d_pkt_len;                       /* device: one per request */
+} ptls_hip_quic_tx_params_t;
+typedef struct st_ptls_hip_quic_tx_report_t {
+    uint64_t n_sent;
+    uint64_t bytes;
+    int32_t lanes;
+    int32_t reserved;
+} ptls_hip_quic_tx_report_t;
+ptls_hip_quic_tx_t *ptls_hip_quic_tx_new(ptls_hip_engine_t *engine, size_t cap);
+void ptls_hip_quic_tx_free(ptls_hip_quic_tx_t *tx);
+int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
+                          const ptls_hip_quic_tx_params_t *params, const ptls_hip_quic_txreq_t *d_reqs, size_t n, const void *d_in,
+                          size_t in_len, void *d_pkt, size_t buf_len, ptls_hip_quic_tx_report_t *report, void *stream);
+const ptls_hip_quic_packet_t *ptls_hip_quic_tx_packets(ptls_hip_quic_tx_t *tx);
+size_t ptls_hip_quic_tx_count(ptls_hip_quic_tx_t *tx);
+void ptls_hip_quic_tx_timing(int enable, float *front_ms, float *sort_ms);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
