@@ -12,6 +12,9 @@
  *   quic.cpp           QUIC packet protection batches: header protection on the device around the record calls, and the two
  *                      header steps every QUIC path launches through (quic_unprotect, quic_protect)
  *                      (kernels: quic_kernel.hip; the header arithmetic shared with the CPU check: quic.h)
+ *   quic_scratch.cpp   what the QUIC device objects below share: the scan levels, the owner of an object's device arrays and
+ *                      timing events (DeviceScratch), the plan sort, the keyset and overlap refusals (quic_scratch.h; the
+ *                      device-side counterpart of the scan lookup: quic_scan.h)
  *   quic_parse.cpp     QUIC datagrams parsed on the device into the packet descriptors of quic.cpp, and the connection-ID map
  *                      (kernels: quic_parse_kernel.hip; the walk and the map arithmetic shared with the CPU check: quic_parse.h)
  *   quic_rx.cpp        the QUIC receive object: parsed entries kept on the device, selected, packed, planned and opened there
@@ -222,6 +225,7 @@ class DeviceGuard {
     int prev_ = 0, dev_ = 0;
 };
 
+#include "quic_scratch.h" /* (quic_scratch.cpp: its types belong here, its functions are hidden as those below) */
 
 #pragma GCC visibility push(hidden)
 
@@ -373,15 +377,6 @@ int run_plan(const LaunchPlan &p, ptls_hip_keyset_t *ks, const void *in, const v
              bool open, ptls_hip_keyset_t *hp_ks = nullptr, const ptls_hip_supp_t *supp = nullptr, void *mask = nullptr);
 
 /* ---- quic_parse.cpp: the steps of the parse call, shared with the receive object of quic_rx.cpp ---- */
-/* the levels of an exclusive scan over n counts (launch_quic_parse_scan), laid out in one allocation of `words` uint32 */
-struct ScanLevels {
-    uint32_t *l0, *l1, *l2, *total; /* the counts, the span sums (has1), their span sums (has2), the grand total */
-    size_t n, n1, n2, words;
-    bool has1, has2;
-};
-ScanLevels scan_levels(uint32_t *base, size_t n); /* base == nullptr: for `words` alone */
-int launch_scan_levels(const ScanLevels &L, int ncu, void *stream);
-unsigned quic_scan_grid(size_t items, int ncu);
 /* the refusals of ptls_hip_quic_parse_datagrams behind its null-pointer checks */
 int quic_parse_check(const char *who, ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
                      const ptls_hip_quic_datagram_t *dgrams, size_t n, size_t buf_len);

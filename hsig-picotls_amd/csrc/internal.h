@@ -237,6 +237,14 @@ int launch_quic_unprotect(int rounds, const QuicArgs &a, unsigned grid, void *st
 int launch_quic_protect(const ptls_hip_quic_packet_t *pkts, uint32_t n, uint8_t *pkt, const uint8_t *mask, unsigned grid,
                         void *stream);
 
+/* the levels of a finished exclusive scan as a kernel reads them (host: ScanLevels::ref, device: quic_scan.h scan_at): the
+ * prefix of position j is l0[j], plus l1[j / QP_SCAN_SPAN] and l2[j / QP_SCAN_SPAN^2] where those levels exist (else nullptr).
+ * A pass in front of the scans writes its counts or 0 / 1 flags into l0 */
+struct ScanRef {
+    uint32_t *l0;
+    const uint32_t *l1, *l2;
+};
+
 /* ---- the key chosen by Key Phase bit, and key updates committed on the device (quic_phase_kernel.hip; the rule shared
  * with the host and the CPU check: quic_phase.h) ---- */
 
@@ -257,8 +265,7 @@ struct QuicCommitArgs {
     const uint32_t *gen_out;
     uint64_t *mins;     /* 2 x count: the lowest packet number of connection c's next-generation packets at [2 c], of its
                            current-generation packets at [2 c + 1]; UINT64_MAX between calls */
-    uint32_t *l0;       /* the scan levels over the 0 / 1 "updated" flags, as in QuicRxArgs */
-    const uint32_t *l1, *l2;
+    ScanRef scan;       /* over the 0 / 1 "updated" flags */
     uint32_t *updated;  /* the updated connections, ascending */
 };
 
@@ -290,8 +297,7 @@ struct QuicTrackArgs {
     uint32_t *verdict;
     uint64_t *expected_pn; /* or nullptr */
     uint64_t expected_count;
-    uint32_t *l0;         /* the scan levels over the 0 / 1 "has a new packet" flags per connection, as in QuicCommitArgs */
-    const uint32_t *l1, *l2;
+    ScanRef scan;         /* over the 0 / 1 "has a new packet" flags per connection */
     uint32_t *touched;    /* the connections with a new packet, ascending */
 };
 
@@ -325,9 +331,7 @@ struct QuicParseArgs {
     uint32_t n;
     uint32_t short_cid_len, max_per_dgram, require_fixed_bit;
     const uint8_t *buf;
-    uint32_t *l0;       /* count pass: entries of datagram i; after the scans: their exclusive prefix within the span of i */
-    const uint32_t *l1; /* write pass: exclusive prefix of the span sums within their span (nullptr: a single span) */
-    const uint32_t *l2; /* ... and of the sums of those (nullptr: at most QP_SCAN_SPAN spans) */
+    ScanRef scan; /* count pass: entries of datagram i into l0; write pass, after the scans: the position of its first entry */
     const QuicCidEntry *table; /* the connection-ID map, or nullptr */
     uint32_t table_size;
     const uint64_t *expected_pn;
@@ -353,9 +357,7 @@ struct QuicRxArgs {
     const ptls_hip_quic_packet_t *pkts;  /* the loaded entries */
     const ptls_hip_quic_pktinfo_t *info; /* or nullptr */
     uint32_t n;
-    /* the scan levels over the select flags (l0: flag, then exclusive prefix within the span; l1 / l2 as in QuicParseArgs) */
-    uint32_t *l0;
-    const uint32_t *l1, *l2;
+    ScanRef scan;                   /* over the select flags */
     const uint32_t *total;          /* the number of selected entries, once the scans have run */
     uint32_t *sel;                  /* compact: entry index of the j-th selected packet (the caller's d_sel) */
     ptls_hip_quic_packet_t *packed; /* compact: its descriptor */
@@ -369,7 +371,7 @@ int launch_quic_rx_compact(const QuicRxArgs &a, const QuicRxLimits &lim, unsigne
 int launch_quic_rx_stats(const QuicRxArgs &a, unsigned grid, void *stream);
 /* One radix pass over m positions, digit = (keys[v] >> shift) & 63 with v = src[t] (src == nullptr: v = t).  hist: the
  * [digit][tile] counts (64 * ntiles words, ntiles = ceil(m / QRX_TILE)); scatter, after their exclusive scan into hl0 / hl1 /
- * hl2: dst[position] = v, stable */
+ * hl2 (a ScanRef's three levels): dst[position] = v, stable */
 int launch_quic_rx_hist(const uint32_t *keys, const uint32_t *src, uint32_t m, uint32_t shift, uint32_t *hist, void *stream);
 int launch_quic_rx_scatter(const uint32_t *keys, const uint32_t *src, uint32_t m, uint32_t shift, const uint32_t *hl0,
                            const uint32_t *hl1, const uint32_t *hl2, uint32_t *dst, void *stream);
@@ -384,11 +386,10 @@ struct QuicTxArgs {
     const ptls_hip_quic_txreq_t *reqs;
     uint32_t n;
     uint32_t *first;      /* per connection below the limits' nconn: the position of its first run's head; QTX_NO_POS between calls */
-    /* the scan levels over the run-head flags (r*: a head's exclusive prefix is its run's index) and over the sent flags (s*) */
-    uint32_t *r0;
-    const uint32_t *r1, *r2, *nruns;
-    uint32_t *s0;
-    const uint32_t *s1, *s2;
+    /* the scans over the run-head flags (a head's exclusive prefix is its run's index, *nruns their total) and over the sent flags */
+    ScanRef runs;
+    const uint32_t *nruns;
+    ScanRef sent;
     uint32_t *run_start;  /* run r begins at position run_start[r]; run_start[*nruns] = n */
     uint32_t *status;     /* the caller's three output arrays */
     uint64_t *pn_out;

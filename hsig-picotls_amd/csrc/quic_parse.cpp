@@ -178,7 +178,7 @@ namespace {
 struct ParseScratch {
     ptls_hip_engine_t *eng;
     void *d_dgrams = nullptr, *d_levels = nullptr, *d_pkts = nullptr, *d_info = nullptr;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    TimingEvents ev{5};
     explicit ParseScratch(ptls_hip_engine_t *e) : eng(e) {}
     ~ParseScratch()
     {
@@ -186,65 +186,10 @@ struct ParseScratch {
         dev_free(eng, d_levels);
         dev_free(eng, d_pkts);
         dev_free(eng, d_info);
-        for (hipEvent_t e : ev)
-            if (e != nullptr)
-                (void)hipEventDestroy(e);
-    }
-    void mark(int k, hipStream_t s)
-    {
-        if (g_timing && (ev[k] != nullptr || hipEventCreate(&ev[k]) == hipSuccess))
-            (void)hipEventRecord(ev[k], s);
-    }
-    float between(int a, int b)
-    {
-        float ms = 0;
-        if (ev[a] == nullptr || ev[b] == nullptr || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess)
-            return 0;
-        return ms;
     }
 };
 
-unsigned parse_grid(size_t items, int ncu)
-{
-    const size_t cap = (size_t)ncu * 8;
-    return (unsigned)std::max<size_t>(1, std::min(items, cap));
-}
-
 } // namespace
-
-/* the scan levels in one allocation: the counts, the span sums, their span sums, and the total */
-ScanLevels scan_levels(uint32_t *base, size_t n)
-{
-    ScanLevels L{};
-    L.n = n;
-    L.n1 = (n + QP_SCAN_SPAN - 1) / QP_SCAN_SPAN;
-    L.n2 = (L.n1 + QP_SCAN_SPAN - 1) / QP_SCAN_SPAN;
-    L.has1 = L.n1 > 1, L.has2 = L.n2 > 1; /* n2 <= QP_SCAN_SPAN: n < 2^32 */
-    const auto pad4 = [](size_t k) { return (k + 3) & ~(size_t)3; };
-    const size_t o1 = pad4(n), o2 = o1 + pad4(L.has1 ? L.n1 : 0), ot = o2 + pad4(L.has2 ? L.n2 : 0);
-    L.words = ot + 4;
-    L.l0 = base;
-    L.l1 = base + o1;
-    L.l2 = base + o2;
-    L.total = base + ot;
-    return L;
-}
-
-/* one scan launch per level; the top level is a single span whose sum is the total */
-int launch_scan_levels(const ScanLevels &L, int ncu, void *stream)
-{
-    int e = launch_quic_parse_scan(L.l0, (uint32_t)L.n, L.has1 ? L.l1 : L.total, parse_grid(L.n1, ncu), stream);
-    if (e == 0 && L.has1)
-        e = launch_quic_parse_scan(L.l1, (uint32_t)L.n1, L.has2 ? L.l2 : L.total, parse_grid(L.n2, ncu), stream);
-    if (e == 0 && L.has2)
-        e = launch_quic_parse_scan(L.l2, (uint32_t)L.n2, L.total, 1, stream);
-    return e;
-}
-
-unsigned quic_scan_grid(size_t items, int ncu)
-{
-    return parse_grid(items, ncu);
-}
 
 int quic_parse_check(const char *who, ptls_hip_engine_t *eng, const ptls_hip_quic_parse_params_t *pr, ptls_hip_quic_cidmap_t *map,
                      const ptls_hip_quic_datagram_t *dgrams, size_t n, size_t buf_len)
@@ -285,14 +230,12 @@ int quic_parse_count(const char *who, ptls_hip_engine_t *eng, const ptls_hip_qui
     a.max_per_dgram = pr->max_per_dgram;
     a.require_fixed_bit = pr->require_fixed_bit;
     a.buf = static_cast<const uint8_t *>(d_buf);
-    a.l0 = L.l0;
-    a.l1 = L.has1 ? L.l1 : nullptr;
-    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.scan = L.ref();
     a.table = map != nullptr ? map->d_table : nullptr;
     a.table_size = map != nullptr ? (uint32_t)map->table.size() : 0;
     a.expected_pn = pr->d_expected_pn;
     a.expected_count = pr->expected_count;
-    *walk_grid = parse_grid((n + 255) / 256, eng->ncu);
+    *walk_grid = quic_scan_grid((n + 255) / 256, eng->ncu);
 
     mark(0);
     HIP_TRY(hipMemcpyAsync(d_dgrams, dgrams, n * sizeof(ptls_hip_quic_datagram_t), hipMemcpyHostToDevice, s), PTLS_HIP_ENODEV);
@@ -351,7 +294,7 @@ extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_
     unsigned walk_grid = 1;
     uint32_t total = 0;
     if (int rc = quic_parse_count(who, eng, pr, map, dgrams, n, d_buf, sc.d_dgrams, static_cast<uint32_t *>(sc.d_levels), stream, a,
-                                  &walk_grid, &total, [&](int k) { sc.mark(k, s); }))
+                                  &walk_grid, &total, [&](int k) { sc.ev.mark(g_timing, k, s); }))
         return rc;
     if (total > cap) {
         *n_pkts = total;
@@ -360,22 +303,22 @@ extern "C" int ptls_hip_quic_parse_datagrams(ptls_hip_engine_t *eng, const ptls_
     if (total != 0) {
         HIP_TRY(dev_alloc(eng, &sc.d_pkts, (size_t)total * sizeof(ptls_hip_quic_packet_t)), PTLS_HIP_ENOMEM);
         HIP_TRY(dev_alloc(eng, &sc.d_info, (size_t)total * sizeof(ptls_hip_quic_pktinfo_t)), PTLS_HIP_ENOMEM);
-        sc.mark(2, s);
+        sc.ev.mark(g_timing, 2, s);
         if (int rc = quic_parse_write(who, map, a, walk_grid, static_cast<ptls_hip_quic_packet_t *>(sc.d_pkts),
                                       static_cast<ptls_hip_quic_pktinfo_t *>(sc.d_info), stream))
             return rc;
-        sc.mark(3, s);
+        sc.ev.mark(g_timing, 3, s);
         HIP_TRY(hipMemcpyAsync(h_pkts, sc.d_pkts, (size_t)total * sizeof(ptls_hip_quic_packet_t), hipMemcpyDeviceToHost, s),
                 PTLS_HIP_ENODEV);
         HIP_TRY(hipMemcpyAsync(h_info, sc.d_info, (size_t)total * sizeof(ptls_hip_quic_pktinfo_t), hipMemcpyDeviceToHost, s),
                 PTLS_HIP_ENODEV);
-        sc.mark(4, s);
+        sc.ev.mark(g_timing, 4, s);
         HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
     }
     if (g_timing) {
         /* kernels: the upload of the datagram array, count and scans (up to the host's look at the total), and the write pass */
-        g_kernels_ms = sc.between(0, 1) + sc.between(2, 3);
-        g_d2h_ms = sc.between(3, 4);
+        g_kernels_ms = sc.ev.between(0, 1) + sc.ev.between(2, 3);
+        g_d2h_ms = sc.ev.between(3, 4);
     }
     *n_pkts = total;
     return 0;

@@ -16,6 +16,7 @@
 
 #include "internal.h"
 #include "quic_parse.h"
+#include "quic_scan.h"
 
 namespace ptls_hip {
 
@@ -27,7 +28,7 @@ __global__ void __launch_bounds__(QP_WG) quic_parse_count_kernel(const QuicParse
 {
     for (uint64_t i = (uint64_t)blockIdx.x * QP_WG + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * QP_WG) {
         const ptls_hip_quic_datagram_t dg = a.dgrams[i];
-        a.l0[i] = quic_walk_datagram(a.buf + dg.off, dg.len, a.short_cid_len, a.max_per_dgram, a.require_fixed_bit,
+        a.scan.l0[i] = quic_walk_datagram(a.buf + dg.off, dg.len, a.short_cid_len, a.max_per_dgram, a.require_fixed_bit,
                                      [](uint32_t, uint32_t, const QuicWalk &, bool) {});
     }
 }
@@ -71,11 +72,7 @@ __global__ void __launch_bounds__(QP_WG) quic_parse_write_kernel(const QuicParse
 {
     for (uint64_t i = (uint64_t)blockIdx.x * QP_WG + threadIdx.x; i < a.n; i += (uint64_t)gridDim.x * QP_WG) {
         const ptls_hip_quic_datagram_t dg = a.dgrams[i];
-        uint32_t at = a.l0[i];
-        if (a.l1 != nullptr)
-            at += a.l1[i / QP_SCAN_SPAN];
-        if (a.l2 != nullptr)
-            at += a.l2[i / ((uint64_t)QP_SCAN_SPAN * QP_SCAN_SPAN)];
+        const uint32_t at = scan_at(a.scan, i);
         const uint8_t *d = a.buf + dg.off;
         quic_walk_datagram(d, dg.len, a.short_cid_len, a.max_per_dgram, a.require_fixed_bit,
                            [=](uint32_t k, uint32_t pos, const QuicWalk &w, bool more) {

@@ -18,6 +18,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#include "quic_scan.h"
 #include "quic_unprotect.h"
 
 namespace ptls_hip {
@@ -77,7 +78,7 @@ __global__ void __launch_bounds__(QPH_WG) quic_phase_apply_kernel(const QuicComm
     for (uint64_t c = (uint64_t)blockIdx.x * QPH_WG + threadIdx.x; c < a.count; c += (uint64_t)gridDim.x * QPH_WG) {
         const uint64_t min_next = a.mins[2 * c], min_cur = a.mins[2 * c + 1];
         if (place == 0) {
-            a.l0[c] = quic_phase_updates(min_next) ? 1u : 0u;
+            a.scan.l0[c] = quic_phase_updates(min_next) ? 1u : 0u;
             continue;
         }
         if (min_next == UINT64_MAX && min_cur == UINT64_MAX)
@@ -88,11 +89,7 @@ __global__ void __launch_bounds__(QPH_WG) quic_phase_apply_kernel(const QuicComm
         a.mins[2 * c] = UINT64_MAX;
         a.mins[2 * c + 1] = UINT64_MAX;
         if (quic_phase_updates(min_next)) { /* (the flag itself is gone: the scan wrote the prefix over it) */
-            uint32_t at = a.l0[c];
-            if (a.l1 != nullptr)
-                at += a.l1[c / QP_SCAN_SPAN];
-            if (a.l2 != nullptr)
-                at += a.l2[c / ((uint64_t)QP_SCAN_SPAN * QP_SCAN_SPAN)];
+            const uint32_t at = scan_at(a.scan, c);
             if (at < a.count)
                 a.updated[at] = (uint32_t)c;
         }

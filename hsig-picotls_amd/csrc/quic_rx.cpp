@@ -25,16 +25,14 @@ namespace {
 thread_local bool g_timing = false;
 thread_local float g_select_ms = 0, g_plan_ms = 0, g_header_ms = 0, g_commit_ms = 0, g_track_ms = 0;
 
-size_t sort_tiles(size_t m)
-{
-    return (m + QRX_TILE - 1) / QRX_TILE;
-}
-
 } // namespace
 
 struct st_ptls_hip_quic_rx_t {
-    ptls_hip_engine_t *eng = nullptr;
-    size_t max_dgrams = 0, cap = 0;
+    ptls_hip_engine_t *eng;
+    size_t max_dgrams, cap;
+    /* every d_ array below comes from here (rx_free: sc.release()); the timing events: select 0-1, sort 2-3, header kernel
+     * 4-5, commit 6-7, track 8-9 */
+    DeviceScratch sc;
     size_t n = 0;          /* entries loaded */
     bool has_info = false; /* ... with info records */
     int mode = 0;          /* ptls_hip_quic_rx_set_plan */
@@ -48,11 +46,10 @@ struct st_ptls_hip_quic_rx_t {
     ptls_hip_quic_packet_t *d_packed = nullptr;
     uint32_t *d_keys = nullptr;
     ptls_hip_record_t *d_recs = nullptr, *d_recs_ord = nullptr;
-    uint32_t *d_order = nullptr, *d_order_tmp = nullptr;
-    uint32_t *d_hist = nullptr; /* the [digit][tile] counts of a radix pass and their scan */
+    PlanSort plan;
     uint64_t *d_stats = nullptr;
     Chunk *d_chunk = nullptr;
-    size_t order_n = 0; /* != 0: d_order holds the last device-made AES plan order of that many packets */
+    size_t order_n = 0; /* != 0: plan.d_order holds the last device-made AES plan order of that many packets */
     /* the commit's scratch (kp_cap connections): the two minima per connection, UINT64_MAX between calls; the scan levels */
     uint64_t *d_kp_mins = nullptr;
     uint32_t *d_kp_levels = nullptr;
@@ -66,36 +63,13 @@ struct st_ptls_hip_quic_rx_t {
     size_t tk_cap = 0, tk_slots = 0;
     bool opened = false; /* an open call has run since the entries were loaded: d_packed holds its open_m selected packets */
     size_t open_m = 0;
-    hipEvent_t ev[10] = {}; /* select 0-1, sort 2-3, header kernel 4-5, commit 6-7, track 8-9 */
-    Uses uses; /* the launches that read or write the arrays above: rx_free waits for them */
 
-    template <class T>
-    int ensure(T **p, size_t bytes)
-    {
-        if (*p != nullptr)
-            return 0;
-        bytes = (bytes + 15) & ~(size_t)15; /* whole 16-byte units: ptls_hip_device_copy can read any array back */
-        if (dev_alloc(eng, reinterpret_cast<void **>(p), bytes) != hipSuccess)
-            return fail(PTLS_HIP_ENOMEM, "quic_rx: cannot allocate %zu bytes of device memory", bytes);
-        return 0;
-    }
+    st_ptls_hip_quic_rx_t(ptls_hip_engine_t *e, size_t dgrams, size_t c) : eng(e), max_dgrams(dgrams), cap(c), sc(e, "quic_rx", 10) {}
     int ensure_entries()
     {
-        if (int e = ensure(&d_pkts, cap * sizeof(ptls_hip_quic_packet_t)))
+        if (int e = sc.ensure(&d_pkts, cap * sizeof(ptls_hip_quic_packet_t)))
             return e;
-        return ensure(&d_info, cap * sizeof(ptls_hip_quic_pktinfo_t));
-    }
-    void mark(int k, hipStream_t s)
-    {
-        if (g_timing && (ev[k] != nullptr || hipEventCreate(&ev[k]) == hipSuccess))
-            (void)hipEventRecord(ev[k], s);
-    }
-    float between(int a, int b)
-    {
-        float ms = 0;
-        if (ev[a] == nullptr || ev[b] == nullptr || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess)
-            return 0;
-        return ms;
+        return sc.ensure(&d_info, cap * sizeof(ptls_hip_quic_pktinfo_t));
     }
 };
 
@@ -106,33 +80,14 @@ extern "C" ptls_hip_quic_rx_t *ptls_hip_quic_rx_new(ptls_hip_engine_t *eng, size
              max_dgrams);
         return nullptr;
     }
-    auto *rx = new st_ptls_hip_quic_rx_t();
-    rx->eng = eng;
-    rx->max_dgrams = max_dgrams;
-    rx->cap = cap;
-    return rx; /* device memory comes with the first use of each array */
+    return new st_ptls_hip_quic_rx_t(eng, max_dgrams, cap); /* device memory comes with the first use of each array */
 }
 
 extern "C" void ptls_hip_quic_rx_free(ptls_hip_quic_rx_t *rx)
 {
     if (rx == nullptr)
         return;
-    void *const mem[] = {rx->d_pkts,  rx->d_info,     rx->d_dgrams, rx->d_parse_levels, rx->d_sel_levels, rx->d_packed, rx->d_keys,
-                         rx->d_recs,  rx->d_recs_ord, rx->d_order,  rx->d_order_tmp,    rx->d_hist,       rx->d_stats,  rx->d_chunk,
-                         rx->d_kp_mins, rx->d_kp_levels, rx->d_tk_acc, rx->d_tk_levels, rx->d_tk_table};
-    bool any = false;
-    for (void *p : mem)
-        any = any || p != nullptr;
-    if (any) {
-        DeviceGuard g(rx->eng->device);
-        rx->uses.wait();
-        for (void *p : mem)
-            dev_free(rx->eng, p);
-        for (hipEvent_t e : rx->ev)
-            if (e != nullptr)
-                (void)hipEventDestroy(e);
-        (void)hipStreamSynchronize(rx->eng->util);
-    }
+    rx->sc.release();
     delete rx;
 }
 
@@ -160,16 +115,16 @@ extern "C" int ptls_hip_quic_rx_parse(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
 
     ptls_hip_engine_t *eng = rx->eng;
     DeviceGuard g(eng->device);
-    if (int e = rx->ensure(&rx->d_dgrams, rx->max_dgrams * sizeof(ptls_hip_quic_datagram_t)))
+    if (int e = rx->sc.ensure(&rx->d_dgrams, rx->max_dgrams * sizeof(ptls_hip_quic_datagram_t)))
         return e;
-    if (int e = rx->ensure(&rx->d_parse_levels, scan_levels(nullptr, rx->max_dgrams).words * sizeof(uint32_t)))
+    if (int e = rx->sc.ensure(&rx->d_parse_levels, scan_levels(nullptr, rx->max_dgrams).words * sizeof(uint32_t)))
         return e;
     if (int e = rx->ensure_entries())
         return e;
     QuicParseArgs a{};
     unsigned walk_grid = 1;
     uint32_t total = 0;
-    rx->uses.note(stream);
+    rx->sc.uses.note(stream);
     if (int rc = quic_parse_count(who, eng, pr, map, dgrams, n, d_buf, rx->d_dgrams, rx->d_parse_levels, stream, a, &walk_grid, &total,
                                   [](int) {}))
         return rc;
@@ -180,7 +135,7 @@ extern "C" int ptls_hip_quic_rx_parse(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
     if (total != 0) {
         if (int rc = quic_parse_write(who, map, a, walk_grid, rx->d_pkts, rx->d_info, stream))
             return rc;
-        rx->uses.note(stream);
+        rx->sc.uses.note(stream);
     }
     rx->n = total;
     *n_pkts = total;
@@ -209,7 +164,7 @@ extern "C" int ptls_hip_quic_rx_set_packets(ptls_hip_quic_rx_t *rx, const ptls_h
     HIP_TRY(hipMemcpyAsync(rx->d_pkts, d_pkts, n * sizeof(ptls_hip_quic_packet_t), hipMemcpyDeviceToDevice, s), PTLS_HIP_ENODEV);
     if (d_info != nullptr)
         HIP_TRY(hipMemcpyAsync(rx->d_info, d_info, n * sizeof(ptls_hip_quic_pktinfo_t), hipMemcpyDeviceToDevice, s), PTLS_HIP_ENODEV);
-    rx->uses.note(stream);
+    rx->sc.uses.note(stream);
     rx->n = n;
     return 0;
 }
@@ -239,7 +194,7 @@ extern "C" int ptls_hip_quic_rx_set_plan(ptls_hip_quic_rx_t *rx, int mode)
 
 extern "C" const uint32_t *ptls_hip_quic_rx_order(ptls_hip_quic_rx_t *rx)
 {
-    return rx != nullptr && rx->order_n != 0 ? rx->d_order : nullptr;
+    return rx != nullptr && rx->order_n != 0 ? rx->plan.d_order : nullptr;
 }
 
 extern "C" void ptls_hip_quic_rx_timing(int enable, float *select_ms, float *plan_ms)
@@ -257,18 +212,6 @@ extern "C" void ptls_hip_quic_rx_keyphase_timing(float *header_ms, float *commit
         *header_ms = g_header_ms;
     if (commit_ms != nullptr)
         *commit_ms = g_commit_ms;
-}
-
-/* one stable radix pass over m positions: counts, their scan, placement */
-static int radix_pass(ptls_hip_quic_rx_t *rx, const uint32_t *src, uint32_t m, uint32_t shift, uint32_t *dst, void *stream)
-{
-    const ScanLevels H = scan_levels(rx->d_hist, QRX_DIGITS * sort_tiles(m));
-    int e = launch_quic_rx_hist(rx->d_keys, src, m, shift, H.l0, stream);
-    if (e == 0)
-        e = launch_scan_levels(H, rx->eng->ncu, stream);
-    if (e == 0)
-        e = launch_quic_rx_scatter(rx->d_keys, src, m, shift, H.l0, H.has1 ? H.l1 : nullptr, H.has2 ? H.l2 : nullptr, dst, stream);
-    return e;
 }
 
 /* the packed descriptors back to the host and through the existing calls, planned there */
@@ -305,12 +248,8 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
         if (rx->mode == 2)
             return fail(PTLS_HIP_EINVAL, "%s: the host plan (rx_set_plan 2) fixes a chunk's key on the host", who);
     }
-    if (ks->eng != rx->eng || hp_ks->eng != rx->eng)
-        return fail(PTLS_HIP_EINVAL, "%s: receive object and keysets must belong to the same engine", who);
-    if (hp_ks->algo != ks->algo || hp_ks->key_size != ks->key_size)
-        return fail(PTLS_HIP_EINVAL, "%s: the header-protection keyset must be of the AEAD keyset's algorithm and key size", who);
-    if (kp != nullptr && kp->stride > ks->nslots / 3) /* (3 * stride <= nslots, without the product) */
-        return fail(PTLS_HIP_EINVAL, "%s: three banks of stride %zu do not fit the keyset's %zu slots", who, kp->stride, ks->nslots);
+    if (int rc = quic_keysets_check(who, "receive object", rx->eng, ks, hp_ks, kp != nullptr ? kp->stride : 0))
+        return rc;
     report->n_selected = 0;
     report->planned_on_device = 0;
     report->lanes = 0;
@@ -320,27 +259,17 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
         return 0;
     if (d_buf == nullptr || d_out == nullptr || d_sel == nullptr || d_result == nullptr || d_pn_out == nullptr)
         return fail(PTLS_HIP_EINVAL, "%s: null buffer", who);
-    {
-        const uintptr_t b = reinterpret_cast<uintptr_t>(d_buf), o = reinterpret_cast<uintptr_t>(d_out);
-        if (buf_len != 0 && out_len != 0 && b < o + out_len && o < b + buf_len)
-            return fail(PTLS_HIP_EINVAL, "%s: the output buffer overlaps the packet buffer", who);
-    }
+    if (int rc = quic_overlap_check(who, "output buffer", d_out, out_len, "packet buffer", d_buf, buf_len))
+        return rc;
 
     ptls_hip_engine_t *eng = rx->eng;
     DeviceGuard g(eng->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const size_t cap = rx->cap;
-    int e = rx->ensure(&rx->d_sel_levels, scan_levels(nullptr, cap).words * sizeof(uint32_t));
-    if (e == 0)
-        e = rx->ensure(&rx->d_packed, cap * sizeof(ptls_hip_quic_packet_t));
-    if (e == 0)
-        e = rx->ensure(&rx->d_keys, cap * sizeof(uint32_t));
-    if (e == 0)
-        e = rx->ensure(&rx->d_recs, cap * sizeof(ptls_hip_record_t));
-    if (e == 0)
-        e = rx->ensure(&rx->d_stats, QRX_NSTATS * sizeof(uint64_t));
-    if (e == 0)
-        e = rx->ensure(&rx->d_chunk, sizeof(Chunk));
+    int e = rx->sc.ensure_all({{&rx->d_sel_levels, scan_levels(nullptr, cap).words * sizeof(uint32_t)},
+                               {&rx->d_packed, cap * sizeof(ptls_hip_quic_packet_t)}, {&rx->d_keys, cap * sizeof(uint32_t)},
+                               {&rx->d_recs, cap * sizeof(ptls_hip_record_t)}, {&rx->d_stats, QRX_NSTATS * sizeof(uint64_t)},
+                               {&rx->d_chunk, sizeof(Chunk)}});
     if (e != 0)
         return e;
     rx->order_n = 0;
@@ -358,9 +287,7 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
     a.pkts = rx->d_pkts;
     a.info = rx->has_info ? rx->d_info : nullptr;
     a.n = (uint32_t)rx->n;
-    a.l0 = L.l0;
-    a.l1 = L.has1 ? L.l1 : nullptr;
-    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.scan = L.ref();
     a.total = L.total;
     a.sel = d_sel;
     a.packed = rx->d_packed;
@@ -368,7 +295,7 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
     a.stats = rx->d_stats;
     a.chunk = rx->d_chunk;
     const unsigned grid = quic_scan_grid((rx->n + 255) / 256, eng->ncu);
-    rx->mark(0, s);
+    rx->sc.ev.mark(g_timing, 0, s);
     e = launch_quic_rx_select(a, lim, grid, stream);
     if (e == 0)
         e = launch_scan_levels(L, eng->ncu, stream);
@@ -378,13 +305,13 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
         e = launch_quic_rx_stats(a, grid, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-    rx->uses.note(stream);
-    rx->mark(1, s);
+    rx->sc.uses.note(stream);
+    rx->sc.ev.mark(g_timing, 1, s);
     uint64_t st[QRX_NSTATS] = {};
     HIP_TRY(hipMemcpyAsync(st, rx->d_stats, sizeof(st), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
     HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
     if (g_timing)
-        g_select_ms = rx->between(0, 1), g_plan_ms = 0;
+        g_select_ms = rx->sc.ev.between(0, 1), g_plan_ms = 0;
     const size_t m = (size_t)st[QRX_STAT_COUNT];
     report->n_selected = m;
     rx->kp_open = kp != nullptr;
@@ -414,29 +341,18 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
     p.ncus = (unsigned)eng->ncu;
     if (!chacha) {
         /* the sparse kernel's plan: a stable order by decreasing 16-byte block count, two radix digits of the 12-bit key */
-        e = rx->ensure(&rx->d_recs_ord, cap * sizeof(ptls_hip_record_t));
-        const bool fresh = rx->d_order == nullptr;
+        e = rx->sc.ensure(&rx->d_recs_ord, cap * sizeof(ptls_hip_record_t));
         if (e == 0)
-            e = rx->ensure(&rx->d_order, cap * sizeof(uint32_t));
-        if (e == 0)
-            e = rx->ensure(&rx->d_order_tmp, cap * sizeof(uint32_t));
-        if (e == 0 && fresh) { /* once: every word the header kernel could ever read as a position is a valid one */
-            HIP_TRY(hipMemsetAsync(rx->d_order, 0, cap * sizeof(uint32_t), s), PTLS_HIP_ENODEV);
-            HIP_TRY(hipMemsetAsync(rx->d_order_tmp, 0, cap * sizeof(uint32_t), s), PTLS_HIP_ENODEV);
-        }
-        if (e == 0)
-            e = rx->ensure(&rx->d_hist, scan_levels(nullptr, QRX_DIGITS * sort_tiles(cap)).words * sizeof(uint32_t));
+            e = rx->plan.ensure(rx->sc, cap, s);
         if (e != 0)
             return e;
-        rx->mark(2, s);
-        e = radix_pass(rx, nullptr, (uint32_t)m, 0, rx->d_order_tmp, stream);
-        if (e == 0)
-            e = radix_pass(rx, rx->d_order_tmp, (uint32_t)m, QRX_DIGIT_BITS, rx->d_order, stream);
+        rx->sc.ev.mark(g_timing, 2, s);
+        e = rx->plan.sort(rx->d_keys, (uint32_t)m, eng->ncu, stream);
         if (e != 0)
             return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-        rx->mark(3, s);
+        rx->sc.ev.mark(g_timing, 3, s);
         p.d_recs_ord = rx->d_recs_ord;
-        p.d_order = rx->d_order;
+        p.d_order = rx->plan.d_order;
         p.d_chunks = rx->d_chunk;
         p.nchunks = 1;
     }
@@ -447,28 +363,24 @@ static int rx_open(const char *who, ptls_hip_quic_rx_t *rx, ptls_hip_keyset_t *k
         ph.gen_out = kp->d_gen_out;
     }
     if (kp != nullptr)
-        rx->mark(4, s);
+        rx->sc.ev.mark(g_timing, 4, s);
     e = quic_unprotect(eng, hp_ks, rx->d_packed, m, p.d_recs, p.d_recs_ord, p.d_order, d_buf, d_pn_out, stream, /* (ChaCha: no order) */
                        kp != nullptr ? &ph : nullptr);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
     if (kp != nullptr)
-        rx->mark(5, s);
+        rx->sc.ev.mark(g_timing, 5, s);
     keyset_note_use(hp_ks, stream);
-    rx->uses.note(stream);
+    rx->sc.uses.note(stream);
     if (int rc = run_plan(p, ks, d_buf, d_buf, d_out, d_result, stream, true))
         return rc;
-    rx->uses.note(stream);
+    rx->sc.uses.note(stream);
     if (!chacha)
         rx->order_n = m;
-    if (g_timing && !chacha && rx->ev[3] != nullptr) { /* (a diagnostic: it waits for the sort, not for the open kernel) */
-        (void)hipEventSynchronize(rx->ev[3]);
-        g_plan_ms = rx->between(2, 3);
-    }
-    if (g_timing && kp != nullptr && rx->ev[5] != nullptr) { /* (likewise: it waits for the header kernel) */
-        (void)hipEventSynchronize(rx->ev[5]);
-        g_header_ms = rx->between(4, 5);
-    }
+    if (!chacha && rx->sc.ev.reached(g_timing, 3)) /* (a diagnostic: it waits for the sort, not for the open kernel) */
+        g_plan_ms = rx->sc.ev.between(2, 3);
+    if (kp != nullptr && rx->sc.ev.reached(g_timing, 5)) /* (likewise: it waits for the header kernel) */
+        g_header_ms = rx->sc.ev.between(4, 5);
     report->planned_on_device = 1;
     report->lanes = chacha ? chacha_lanes : SPARSE_LANES;
     return 0;
@@ -513,21 +425,9 @@ extern "C" int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip
     ptls_hip_engine_t *eng = rx->eng;
     DeviceGuard g(eng->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (count > rx->kp_cap) { /* (grown: the launches that used the smaller arrays are waited for first) */
-        if (rx->d_kp_mins != nullptr || rx->d_kp_levels != nullptr) {
-            rx->uses.wait();
-            dev_free(eng, rx->d_kp_mins);
-            dev_free(eng, rx->d_kp_levels);
-            rx->d_kp_mins = nullptr, rx->d_kp_levels = nullptr, rx->kp_cap = 0;
-        }
-        int e = rx->ensure(&rx->d_kp_mins, 2 * count * sizeof(uint64_t));
-        if (e == 0)
-            e = rx->ensure(&rx->d_kp_levels, scan_levels(nullptr, count).words * sizeof(uint32_t));
-        if (e != 0)
-            return e;
-        HIP_TRY(hipMemsetAsync(rx->d_kp_mins, 0xff, 2 * count * sizeof(uint64_t), s), PTLS_HIP_ENODEV); /* once: UINT64_MAX */
-        rx->kp_cap = count;
-    }
+    if (int e = rx->sc.grow(&rx->kp_cap, count, s, {{&rx->d_kp_mins, 2 * count * sizeof(uint64_t), 0xff}, /* UINT64_MAX */
+                                                    {&rx->d_kp_levels, scan_levels(nullptr, count).words * sizeof(uint32_t)}}))
+        return e;
     const ScanLevels L = scan_levels(rx->d_kp_levels, count);
     QuicCommitArgs a{};
     a.phase = d_phase;
@@ -537,14 +437,12 @@ extern "C" int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip
     a.pn_out = d_pn_out;
     a.gen_out = d_gen_out;
     a.mins = rx->d_kp_mins;
-    a.l0 = L.l0;
-    a.l1 = L.has1 ? L.l1 : nullptr;
-    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.scan = L.ref();
     a.updated = d_updated;
     /* the mark pass: QPH_MARK_PER_THREAD packets per thread, so that a lane has successive packets to fold (internal.h) */
     const unsigned pkt_grid = quic_scan_grid((m + 256 * QPH_MARK_PER_THREAD - 1) / (256 * QPH_MARK_PER_THREAD), eng->ncu);
     const unsigned conn_grid = quic_scan_grid((count + 255) / 256, eng->ncu);
-    rx->mark(6, s);
+    rx->sc.ev.mark(g_timing, 6, s);
     int e = launch_quic_phase_mark(a, (uint32_t)m, pkt_grid, stream);
     if (e == 0)
         e = launch_quic_phase_apply(a, 0, conn_grid, stream);
@@ -554,13 +452,13 @@ extern "C" int ptls_hip_quic_rx_keyphase_commit(ptls_hip_quic_rx_t *rx, ptls_hip
         e = launch_quic_phase_apply(a, 1, conn_grid, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-    rx->uses.note(stream);
-    rx->mark(7, s);
+    rx->sc.uses.note(stream);
+    rx->sc.ev.mark(g_timing, 7, s);
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, L.total, sizeof(total), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
     HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
     if (g_timing)
-        g_commit_ms = rx->between(6, 7);
+        g_commit_ms = rx->sc.ev.between(6, 7);
     *n_updated = total;
     return 0;
 }
@@ -595,32 +493,12 @@ extern "C" int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
     ptls_hip_engine_t *eng = rx->eng;
     DeviceGuard g(eng->device);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (count > rx->tk_cap) { /* (grown: the launches that used the smaller arrays are waited for first) */
-        if (rx->d_tk_acc != nullptr || rx->d_tk_levels != nullptr) {
-            rx->uses.wait();
-            dev_free(eng, rx->d_tk_acc);
-            dev_free(eng, rx->d_tk_levels);
-            rx->d_tk_acc = nullptr, rx->d_tk_levels = nullptr, rx->tk_cap = 0;
-        }
-        int e = rx->ensure(&rx->d_tk_acc, 6 * count * sizeof(uint64_t));
-        if (e == 0)
-            e = rx->ensure(&rx->d_tk_levels, scan_levels(nullptr, count).words * sizeof(uint32_t));
-        if (e != 0)
-            return e;
-        HIP_TRY(hipMemsetAsync(rx->d_tk_acc, 0, 6 * count * sizeof(uint64_t), s), PTLS_HIP_ENODEV); /* once */
-        rx->tk_cap = count;
-    }
+    if (int e = rx->sc.grow(&rx->tk_cap, count, s, {{&rx->d_tk_acc, 6 * count * sizeof(uint64_t), 0},
+                                                    {&rx->d_tk_levels, scan_levels(nullptr, count).words * sizeof(uint32_t)}}))
+        return e;
     const uint64_t slots = quic_track_slots(m);
-    if (slots > rx->tk_slots) {
-        if (rx->d_tk_table != nullptr) {
-            rx->uses.wait();
-            dev_free(eng, rx->d_tk_table);
-            rx->d_tk_table = nullptr, rx->tk_slots = 0;
-        }
-        if (int e = rx->ensure(&rx->d_tk_table, slots * sizeof(uint32_t)))
-            return e;
-        rx->tk_slots = slots;
-    }
+    if (int e = rx->sc.grow(&rx->tk_slots, slots, s, {{&rx->d_tk_table, slots * sizeof(uint32_t)}})) /* (filled per call, below) */
+        return e;
     const ScanLevels L = scan_levels(rx->d_tk_levels, count);
     QuicTrackArgs a{};
     a.spaces = tr->d_spaces;
@@ -637,14 +515,12 @@ extern "C" int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
     a.verdict = tr->d_verdict;
     a.expected_pn = tr->d_expected_pn;
     a.expected_count = tr->expected_count;
-    a.l0 = L.l0;
-    a.l1 = L.has1 ? L.l1 : nullptr;
-    a.l2 = L.has2 ? L.l2 : nullptr;
+    a.scan = L.ref();
     a.touched = tr->d_touched;
     const unsigned claim_grid = quic_scan_grid((m + 256 * QTK_CLAIM_PER_THREAD - 1) / (256 * QTK_CLAIM_PER_THREAD), eng->ncu);
     const unsigned pkt_grid = quic_scan_grid((m + 255) / 256, eng->ncu);
     const unsigned conn_grid = quic_scan_grid((count + 255) / 256, eng->ncu);
-    rx->mark(8, s);
+    rx->sc.ev.mark(g_timing, 8, s);
     HIP_TRY(hipMemsetAsync(rx->d_tk_table, 0xff, slots * sizeof(uint32_t), s), PTLS_HIP_ENODEV); /* every slot QTK_EMPTY */
     int e = launch_quic_track_claim(a, (uint32_t)m, claim_grid, stream);
     if (e == 0)
@@ -657,13 +533,13 @@ extern "C" int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
         e = launch_quic_track_apply(a, 1, conn_grid, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-    rx->uses.note(stream);
-    rx->mark(9, s);
+    rx->sc.uses.note(stream);
+    rx->sc.ev.mark(g_timing, 9, s);
     uint32_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, L.total, sizeof(total), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
     HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
     if (g_timing)
-        g_track_ms = rx->between(8, 9);
+        g_track_ms = rx->sc.ev.between(8, 9);
     *n_touched = total;
     return 0;
 }

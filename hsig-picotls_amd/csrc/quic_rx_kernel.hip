@@ -22,6 +22,7 @@
 
 #include "internal.h"
 #include "quic_rx.h"
+#include "quic_scan.h"
 
 namespace ptls_hip {
 
@@ -37,7 +38,7 @@ __global__ void __launch_bounds__(QRX_WG) quic_rx_select_kernel(const QuicRxArgs
         a.stats[threadIdx.x] = 0;
     for (uint64_t k = (uint64_t)blockIdx.x * QRX_WG + threadIdx.x; k < a.n; k += (uint64_t)gridDim.x * QRX_WG) {
         const uint32_t type = a.info != nullptr ? a.info[k].type : 0u;
-        a.l0[k] = quic_rx_selectable(a.pkts[k], type, lim) ? 1u : 0u;
+        a.scan.l0[k] = quic_rx_selectable(a.pkts[k], type, lim) ? 1u : 0u;
     }
 }
 
@@ -48,23 +49,11 @@ __global__ void __launch_bounds__(QRX_WG) quic_rx_compact_kernel(const QuicRxArg
         const uint32_t type = a.info != nullptr ? a.info[k].type : 0u;
         if (!quic_rx_selectable(p, type, lim)) /* (the flag itself is gone: the scan wrote the prefix over it) */
             continue;
-        uint32_t at = a.l0[k];
-        if (a.l1 != nullptr)
-            at += a.l1[k / QP_SCAN_SPAN];
-        if (a.l2 != nullptr)
-            at += a.l2[k / ((uint64_t)QP_SCAN_SPAN * QP_SCAN_SPAN)];
+        const uint32_t at = scan_at(a.scan, k);
         a.sel[at] = (uint32_t)k;
         a.packed[at] = p;
         a.keys[at] = quic_rx_sort_key(p);
     }
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v += __shfl_xor(v, d);
-    return v;
 }
 
 __global__ void __launch_bounds__(QRX_WG) quic_rx_stats_kernel(const QuicRxArgs a)
@@ -167,7 +156,7 @@ __global__ void __launch_bounds__(QRX_WG) quic_rx_scatter_kernel(const uint32_t 
         if (d[r] >= QRX_DIGITS)
             continue;
         const uint64_t x = (uint64_t)d[r] * ntiles + tile;
-        uint32_t at = hl0[x] + rank[r];
+        uint32_t at = hl0[x] + rank[r]; /* (scan_at written out: the three levels are this kernel's own __restrict__ pointers) */
         if (hl1 != nullptr)
             at += hl1[x / QP_SCAN_SPAN];
         if (hl2 != nullptr)

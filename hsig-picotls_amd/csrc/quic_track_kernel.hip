@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "quic_scan.h"
 #include "quic_track.h"
 
 namespace ptls_hip {
@@ -137,7 +138,7 @@ __global__ void __launch_bounds__(QTK_WG) quic_track_apply_kernel(const QuicTrac
         const uint64_t top0 = a.acc[6 * c], top1 = a.acc[6 * c + 2], top2 = a.acc[6 * c + 4];
         const bool any = (top0 | top1 | top2) != 0;
         if (place == 0) {
-            a.l0[c] = any ? 1u : 0u;
+            a.scan.l0[c] = any ? 1u : 0u;
             continue;
         }
         if (!any)
@@ -155,11 +156,7 @@ __global__ void __launch_bounds__(QTK_WG) quic_track_apply_kernel(const QuicTrac
             a.acc[2 * p] = 0;
             a.acc[2 * p + 1] = 0;
         }
-        uint32_t at = a.l0[c]; /* (the flag itself is gone: the scan wrote the prefix over it) */
-        if (a.l1 != nullptr)
-            at += a.l1[c / QP_SCAN_SPAN];
-        if (a.l2 != nullptr)
-            at += a.l2[c / ((uint64_t)QP_SCAN_SPAN * QP_SCAN_SPAN)];
+        const uint32_t at = scan_at(a.scan, c); /* (the flag itself is gone: the scan wrote the prefix over it) */
         if (at < a.count)
             a.touched[at] = (uint32_t)c;
     }

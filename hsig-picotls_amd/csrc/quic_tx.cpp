@@ -2,8 +2,8 @@
  * quic_tx.cpp -- the send object (include/ptls_hip.h 2l): requests in device memory become protected
  * short-header packets with one call.  The packet numbers, their encoded lengths, the header bytes and the key generation
  * come from a per-connection state table on the device (the rule: quic_tx.h, shared with quic_tx_kernel.hip); the compacted
- * descriptors then go through what every seal path here uses: the scan levels of quic_parse.cpp, the radix passes of
- * quic_rx_kernel.hip for the wave-per-record AES kernel's plan, batch.cpp's run_plan with header-protection masks, and
+ * descriptors then go through what every seal path here uses: the scan levels and the plan sort of quic_scratch.cpp (the
+ * wave-per-record AES kernel's plan), batch.cpp's run_plan with header-protection masks, and
  * quic.cpp's quic_protect.  The host reads three sums per call and nothing per packet.
  */
 #include <algorithm>
@@ -13,7 +13,6 @@
 #include "host.h"
 
 #define GF128_FN static inline
-#include "quic_rx.h" /* (the sort key's digits) */
 #include "quic_tx.h"
 
 static_assert(sizeof(ptls_hip_quic_txconn_t) == 48 && __builtin_offsetof(ptls_hip_quic_txconn_t, gen) == 16 &&
@@ -30,16 +29,14 @@ namespace {
 thread_local bool g_timing = false;
 thread_local float g_front_ms = 0, g_sort_ms = 0;
 
-size_t sort_tiles(size_t m)
-{
-    return (m + QRX_TILE - 1) / QRX_TILE;
-}
-
 } // namespace
 
 struct st_ptls_hip_quic_tx_t {
-    ptls_hip_engine_t *eng = nullptr;
-    size_t cap = 0;
+    ptls_hip_engine_t *eng;
+    size_t cap;
+    /* every d_ array below comes from here (tx_free: sc.release()); the timing events: the passes in front of the record
+     * kernel 0-1, the sort 2-3 */
+    DeviceScratch sc;
     size_t m = 0; /* sent packets of the last call: d_packed holds their descriptors */
     /* per request (cap): the two scan-level sets, the run starts (cap + 1) */
     uint32_t *d_run_levels = nullptr, *d_sent_levels = nullptr, *d_run_start = nullptr;
@@ -48,37 +45,15 @@ struct st_ptls_hip_quic_tx_t {
     ptls_hip_record_t *d_recs = nullptr, *d_recs_ord = nullptr;
     ptls_hip_supp_t *d_supp = nullptr;
     uint8_t *d_mask = nullptr;
-    uint32_t *d_keys = nullptr, *d_order = nullptr, *d_order_tmp = nullptr, *d_hist = nullptr;
+    uint32_t *d_keys = nullptr;
+    PlanSort plan;
     uint64_t *d_stats = nullptr;
     Chunk *d_chunk = nullptr;
     /* per connection (first_cap): the position of its first run's head, QTX_NO_POS between calls */
     uint32_t *d_first = nullptr;
     size_t first_cap = 0;
-    hipEvent_t ev[4] = {}; /* the passes in front of the record kernel 0-1, the sort 2-3 */
-    Uses uses;             /* the launches that read or write the arrays above: tx_free waits for them */
 
-    template <class T>
-    int ensure(T **p, size_t bytes)
-    {
-        if (*p != nullptr)
-            return 0;
-        bytes = (bytes + 15) & ~(size_t)15; /* whole 16-byte units: ptls_hip_device_copy can read any array back */
-        if (dev_alloc(eng, reinterpret_cast<void **>(p), bytes) != hipSuccess)
-            return fail(PTLS_HIP_ENOMEM, "quic_tx: cannot allocate %zu bytes of device memory", bytes);
-        return 0;
-    }
-    void mark(int k, hipStream_t s)
-    {
-        if (g_timing && (ev[k] != nullptr || hipEventCreate(&ev[k]) == hipSuccess))
-            (void)hipEventRecord(ev[k], s);
-    }
-    float between(int a, int b)
-    {
-        float ms = 0;
-        if (ev[a] == nullptr || ev[b] == nullptr || hipEventElapsedTime(&ms, ev[a], ev[b]) != hipSuccess)
-            return 0;
-        return ms;
-    }
+    st_ptls_hip_quic_tx_t(ptls_hip_engine_t *e, size_t requests) : eng(e), cap(requests), sc(e, "quic_tx", 4) {}
 };
 
 extern "C" ptls_hip_quic_tx_t *ptls_hip_quic_tx_new(ptls_hip_engine_t *eng, size_t cap)
@@ -87,31 +62,14 @@ extern "C" ptls_hip_quic_tx_t *ptls_hip_quic_tx_new(ptls_hip_engine_t *eng, size
         fail(PTLS_HIP_EINVAL, "quic_tx_new: null engine, or cap %zu outside 1 .. 2^32 - 1", cap);
         return nullptr;
     }
-    auto *tx = new st_ptls_hip_quic_tx_t();
-    tx->eng = eng;
-    tx->cap = cap;
-    return tx; /* device memory comes with the first use of each array */
+    return new st_ptls_hip_quic_tx_t(eng, cap); /* device memory comes with the first use of each array */
 }
 
 extern "C" void ptls_hip_quic_tx_free(ptls_hip_quic_tx_t *tx)
 {
     if (tx == nullptr)
         return;
-    void *const mem[] = {tx->d_run_levels, tx->d_sent_levels, tx->d_run_start, tx->d_packed, tx->d_recs,  tx->d_recs_ord, tx->d_supp, tx->d_mask,
-                         tx->d_keys,       tx->d_order,       tx->d_order_tmp, tx->d_hist,   tx->d_stats, tx->d_chunk,    tx->d_first};
-    bool any = false;
-    for (void *p : mem)
-        any = any || p != nullptr;
-    if (any) {
-        DeviceGuard g(tx->eng->device);
-        tx->uses.wait();
-        for (void *p : mem)
-            dev_free(tx->eng, p);
-        for (hipEvent_t e : tx->ev)
-            if (e != nullptr)
-                (void)hipEventDestroy(e);
-        (void)hipStreamSynchronize(tx->eng->util);
-    }
+    tx->sc.release();
     delete tx;
 }
 
@@ -134,18 +92,6 @@ extern "C" void ptls_hip_quic_tx_timing(int enable, float *front_ms, float *sort
         *sort_ms = g_sort_ms;
 }
 
-/* one stable radix pass over m positions: counts, their scan, placement (quic_rx_kernel.hip's passes) */
-static int radix_pass(ptls_hip_quic_tx_t *tx, const uint32_t *src, uint32_t m, uint32_t shift, uint32_t *dst, void *stream)
-{
-    const ScanLevels H = scan_levels(tx->d_hist, QRX_DIGITS * sort_tiles(m));
-    int e = launch_quic_rx_hist(tx->d_keys, src, m, shift, H.l0, stream);
-    if (e == 0)
-        e = launch_scan_levels(H, tx->eng->ncu, stream);
-    if (e == 0)
-        e = launch_quic_rx_scatter(tx->d_keys, src, m, shift, H.l0, H.has1 ? H.l1 : nullptr, H.has2 ? H.l2 : nullptr, dst, stream);
-    return e;
-}
-
 extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *ks, ptls_hip_keyset_t *hp_ks,
                                      const ptls_hip_quic_tx_params_t *pr, const ptls_hip_quic_txreq_t *d_reqs, size_t n, const void *d_in,
                                      size_t in_len, void *d_pkt, size_t buf_len, ptls_hip_quic_tx_report_t *report, void *stream)
@@ -165,19 +111,13 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
         return fail(PTLS_HIP_EINVAL, "%s: pn_len %u is above 4", who, pr->pn_len);
     if (pr->reserved != 0)
         return fail(PTLS_HIP_EINVAL, "%s: params.reserved is not 0", who);
-    if (ks->eng != tx->eng || hp_ks->eng != tx->eng)
-        return fail(PTLS_HIP_EINVAL, "%s: send object and keysets must belong to the same engine", who);
-    if (hp_ks->algo != ks->algo || hp_ks->key_size != ks->key_size)
-        return fail(PTLS_HIP_EINVAL, "%s: the header-protection keyset must be of the AEAD keyset's algorithm and key size", who);
-    if (pr->stride > ks->nslots / 3) /* (3 * stride <= nslots, without the product) */
-        return fail(PTLS_HIP_EINVAL, "%s: three banks of stride %zu do not fit the keyset's %zu slots", who, pr->stride, ks->nslots);
+    if (int rc = quic_keysets_check(who, "send object", tx->eng, ks, hp_ks, pr->stride))
+        return rc;
     if (n != 0 && (d_reqs == nullptr || d_in == nullptr || d_pkt == nullptr))
         return fail(PTLS_HIP_EINVAL, "%s: null request array or buffer", who);
-    {
-        const uintptr_t i = reinterpret_cast<uintptr_t>(d_in), p = reinterpret_cast<uintptr_t>(d_pkt);
-        if (n != 0 && in_len != 0 && buf_len != 0 && i < p + buf_len && p < i + in_len)
-            return fail(PTLS_HIP_EINVAL, "%s: the packet buffer overlaps the payload buffer", who);
-    }
+    if (n != 0)
+        if (int rc = quic_overlap_check(who, "packet buffer", d_pkt, buf_len, "payload buffer", d_in, in_len))
+            return rc;
     report->n_sent = 0;
     report->bytes = 0;
     report->lanes = 0;
@@ -200,52 +140,21 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
     lim.has_rx_phase = pr->d_rx_phase != nullptr ? 1u : 0u;
 
     const size_t level_words = scan_levels(nullptr, cap).words;
-    int e = tx->ensure(&tx->d_run_levels, level_words * sizeof(uint32_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_sent_levels, level_words * sizeof(uint32_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_run_start, (cap + 1) * sizeof(uint32_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_packed, cap * sizeof(ptls_hip_quic_packet_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_recs, cap * sizeof(ptls_hip_record_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_supp, cap * sizeof(ptls_hip_supp_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_mask, cap * 16);
-    if (e == 0)
-        e = tx->ensure(&tx->d_keys, cap * sizeof(uint32_t));
-    if (e == 0)
-        e = tx->ensure(&tx->d_stats, QTX_NSTATS * sizeof(uint64_t));
+    int e = tx->sc.ensure_all({{&tx->d_run_levels, level_words * sizeof(uint32_t)}, {&tx->d_sent_levels, level_words * sizeof(uint32_t)},
+                               {&tx->d_run_start, (cap + 1) * sizeof(uint32_t)}, {&tx->d_packed, cap * sizeof(ptls_hip_quic_packet_t)},
+                               {&tx->d_recs, cap * sizeof(ptls_hip_record_t)}, {&tx->d_supp, cap * sizeof(ptls_hip_supp_t)},
+                               {&tx->d_mask, cap * 16}, {&tx->d_keys, cap * sizeof(uint32_t)}, {&tx->d_stats, QTX_NSTATS * sizeof(uint64_t)}});
     if (e == 0 && !chacha) {
-        e = tx->ensure(&tx->d_recs_ord, cap * sizeof(ptls_hip_record_t));
-        const bool fresh = tx->d_order == nullptr;
+        e = tx->sc.ensure(&tx->d_recs_ord, cap * sizeof(ptls_hip_record_t));
         if (e == 0)
-            e = tx->ensure(&tx->d_order, cap * sizeof(uint32_t));
+            e = tx->plan.ensure(tx->sc, cap, s);
         if (e == 0)
-            e = tx->ensure(&tx->d_order_tmp, cap * sizeof(uint32_t));
-        if (e == 0 && fresh) { /* once: every word a pass could ever read as a position is a valid one */
-            HIP_TRY(hipMemsetAsync(tx->d_order, 0, cap * sizeof(uint32_t), s), PTLS_HIP_ENODEV);
-            HIP_TRY(hipMemsetAsync(tx->d_order_tmp, 0, cap * sizeof(uint32_t), s), PTLS_HIP_ENODEV);
-        }
-        if (e == 0)
-            e = tx->ensure(&tx->d_hist, scan_levels(nullptr, QRX_DIGITS * sort_tiles(cap)).words * sizeof(uint32_t));
-        if (e == 0)
-            e = tx->ensure(&tx->d_chunk, sizeof(Chunk));
+            e = tx->sc.ensure(&tx->d_chunk, sizeof(Chunk));
     }
     if (e != 0)
         return e;
-    if (lim.nconn > tx->first_cap) { /* (grown: the launches that used the smaller array are waited for first) */
-        if (tx->d_first != nullptr) {
-            tx->uses.wait();
-            dev_free(eng, tx->d_first);
-            tx->d_first = nullptr, tx->first_cap = 0;
-        }
-        if (int e2 = tx->ensure(&tx->d_first, (size_t)lim.nconn * sizeof(uint32_t)))
-            return e2;
-        HIP_TRY(hipMemsetAsync(tx->d_first, 0xff, (size_t)lim.nconn * sizeof(uint32_t), s), PTLS_HIP_ENODEV); /* once: QTX_NO_POS */
-        tx->first_cap = lim.nconn;
-    }
+    if (int e2 = tx->sc.grow(&tx->first_cap, lim.nconn, s, {{&tx->d_first, (size_t)lim.nconn * sizeof(uint32_t), 0xff}})) /* QTX_NO_POS */
+        return e2;
 
     const ScanLevels R = scan_levels(tx->d_run_levels, n), S = scan_levels(tx->d_sent_levels, n);
     QuicTxArgs a{};
@@ -254,13 +163,9 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
     a.reqs = d_reqs;
     a.n = (uint32_t)n;
     a.first = tx->d_first;
-    a.r0 = R.l0;
-    a.r1 = R.has1 ? R.l1 : nullptr;
-    a.r2 = R.has2 ? R.l2 : nullptr;
+    a.runs = R.ref();
     a.nruns = R.total;
-    a.s0 = S.l0;
-    a.s1 = S.has1 ? S.l1 : nullptr;
-    a.s2 = S.has2 ? S.l2 : nullptr;
+    a.sent = S.ref();
     a.run_start = tx->d_run_start;
     a.status = pr->d_status;
     a.pn_out = pr->d_pn_out;
@@ -272,7 +177,7 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
     a.keys = tx->d_keys;
     a.stats = tx->d_stats;
     const unsigned grid = quic_scan_grid((n + 255) / 256, eng->ncu);
-    tx->mark(0, s);
+    tx->sc.ev.mark(g_timing, 0, s);
     e = launch_quic_tx_heads(a, lim, grid, stream);
     if (e == 0)
         e = launch_scan_levels(R, eng->ncu, stream);
@@ -288,13 +193,13 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
         e = launch_quic_tx_apply(a, lim, grid, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-    tx->uses.note(stream);
-    tx->mark(1, s);
+    tx->sc.uses.note(stream);
+    tx->sc.ev.mark(g_timing, 1, s);
     uint64_t st[QTX_NSTATS] = {};
     HIP_TRY(hipMemcpyAsync(st, tx->d_stats, sizeof(st), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
     HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
     if (g_timing)
-        g_front_ms = tx->between(0, 1), g_sort_ms = 0;
+        g_front_ms = tx->sc.ev.between(0, 1), g_sort_ms = 0;
     const size_t m = (size_t)st[QTX_STAT_COUNT];
     report->n_sent = m;
     report->bytes = st[QTX_STAT_BYTES];
@@ -313,18 +218,16 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
     p.ncus = (unsigned)eng->ncu;
     if (!chacha) {
         /* the wave-per-record kernel's plan: a stable order by decreasing 16-byte block count, two radix digits of the key */
-        tx->mark(2, s);
-        e = radix_pass(tx, nullptr, (uint32_t)m, 0, tx->d_order_tmp, stream);
+        tx->sc.ev.mark(g_timing, 2, s);
+        e = tx->plan.sort(tx->d_keys, (uint32_t)m, eng->ncu, stream);
         if (e == 0)
-            e = radix_pass(tx, tx->d_order_tmp, (uint32_t)m, QRX_DIGIT_BITS, tx->d_order, stream);
-        if (e == 0)
-            e = launch_quic_tx_order(tx->d_recs, tx->d_order, (uint32_t)m, tx->d_recs_ord, tx->d_chunk, quic_scan_grid((m + 255) / 256, eng->ncu),
+            e = launch_quic_tx_order(tx->d_recs, tx->plan.d_order, (uint32_t)m, tx->d_recs_ord, tx->d_chunk, quic_scan_grid((m + 255) / 256, eng->ncu),
                                      stream);
         if (e != 0)
             return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-        tx->mark(3, s);
+        tx->sc.ev.mark(g_timing, 3, s);
         p.d_recs_ord = tx->d_recs_ord;
-        p.d_order = tx->d_order;
+        p.d_order = tx->plan.d_order;
         p.d_chunks = tx->d_chunk;
         p.nchunks = 1;
     }
@@ -334,11 +237,9 @@ extern "C" int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *
     e = quic_protect(tx->d_packed, m, d_pkt, tx->d_mask, stream);
     if (e != 0)
         return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
-    tx->uses.note(stream);
-    if (g_timing && !chacha && tx->ev[3] != nullptr) { /* (a diagnostic: it waits for the sort, not for the record kernel) */
-        (void)hipEventSynchronize(tx->ev[3]);
-        g_sort_ms = tx->between(2, 3);
-    }
+    tx->sc.uses.note(stream);
+    if (!chacha && tx->sc.ev.reached(g_timing, 3)) /* (a diagnostic: it waits for the sort, not for the record kernel) */
+        g_sort_ms = tx->sc.ev.between(2, 3);
     report->lanes = chacha ? p.chacha_lanes : SPARSE_LANES;
     return 0;
 }

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "internal.h"
+#include "quic_scan.h"
 #include "quic_tx.h"
 
 namespace ptls_hip {
@@ -36,25 +37,6 @@ namespace {
 __device__ __forceinline__ bool is_head(const QuicTxArgs &a, uint64_t j, uint32_t conn)
 {
     return j == 0 || a.reqs[j - 1].conn != conn;
-}
-
-/* the exclusive prefix of position j over scanned levels */
-__device__ __forceinline__ uint32_t prefix_at(const uint32_t *l0, const uint32_t *l1, const uint32_t *l2, uint64_t j)
-{
-    uint32_t at = l0[j];
-    if (l1 != nullptr)
-        at += l1[j / QP_SCAN_SPAN];
-    if (l2 != nullptr)
-        at += l2[j / ((uint64_t)QP_SCAN_SPAN * QP_SCAN_SPAN)];
-    return at;
-}
-
-__device__ __forceinline__ uint64_t wave_sum(uint64_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v += __shfl_xor(v, d);
-    return v;
 }
 
 /* the generation connection c sends under in this call: from the state before it */
@@ -73,7 +55,7 @@ __global__ void __launch_bounds__(QTX_WG) quic_tx_heads_kernel(const QuicTxArgs 
     for (uint64_t j = (uint64_t)blockIdx.x * QTX_WG + threadIdx.x; j < a.n; j += (uint64_t)gridDim.x * QTX_WG) {
         const uint32_t conn = a.reqs[j].conn;
         const bool head = is_head(a, j, conn);
-        a.r0[j] = head ? 1u : 0u;
+        a.runs.l0[j] = head ? 1u : 0u;
         if (head && conn < lim.nconn)
             atomicMin(a.first + conn, (uint32_t)j);
     }
@@ -83,7 +65,7 @@ __global__ void __launch_bounds__(QTX_WG) quic_tx_runs_kernel(const QuicTxArgs a
 {
     for (uint64_t j = (uint64_t)blockIdx.x * QTX_WG + threadIdx.x; j < a.n; j += (uint64_t)gridDim.x * QTX_WG) {
         if (is_head(a, j, a.reqs[j].conn)) /* (the flag itself is gone: the scan wrote the prefix over it) */
-            a.run_start[prefix_at(a.r0, a.r1, a.r2, j)] = (uint32_t)j;
+            a.run_start[scan_at(a.runs, j)] = (uint32_t)j;
         if (j + 1 == a.n)
             a.run_start[*a.nruns] = a.n;
     }
@@ -97,7 +79,7 @@ __global__ void __launch_bounds__(QTX_WG) quic_tx_select_kernel(const QuicTxArgs
         QuicTxVerdict v{PTLS_HIP_QUIC_TX_NO_CONN, 0, 0};
         uint64_t pn = UINT64_MAX;
         if (r.conn < lim.nconn) {
-            const uint32_t run = prefix_at(a.r0, a.r1, a.r2, j) - (is_head(a, j, r.conn) ? 0u : 1u);
+            const uint32_t run = scan_at(a.runs, j) - (is_head(a, j, r.conn) ? 0u : 1u);
             const uint32_t h = a.run_start[run];
             if (a.first[r.conn] != h) {
                 v.status = PTLS_HIP_QUIC_TX_SPLIT;
@@ -110,7 +92,7 @@ __global__ void __launch_bounds__(QTX_WG) quic_tx_select_kernel(const QuicTxArgs
         a.pn_out[j] = pn;
         a.pkt_len[j] = v.pkt_len;
         const bool sent = v.status == PTLS_HIP_QUIC_TX_SENT;
-        a.s0[j] = sent ? 1u : 0u;
+        a.sent.l0[j] = sent ? 1u : 0u;
         if (sent) {
             ++count;
             bytes += v.pkt_len;
@@ -134,7 +116,7 @@ __global__ void __launch_bounds__(QTX_WG) quic_tx_build_kernel(const QuicTxArgs 
         if (a.status[j] != PTLS_HIP_QUIC_TX_SENT) /* (written by the select pass, a launch ago) */
             continue;
         const ptls_hip_quic_txreq_t r = a.reqs[j];
-        const uint32_t at = prefix_at(a.s0, a.s1, a.s2, j);
+        const uint32_t at = scan_at(a.sent, j);
         if (at >= a.n)
             continue; /* (never: at most n requests are sent) */
         const uint64_t pn = a.pn_out[j];
@@ -167,7 +149,7 @@ __global__ void __launch_bounds__(QTX_WG) quic_tx_apply_kernel(const QuicTxArgs 
         if (conn >= lim.nconn || !is_head(a, j, conn) || a.first[conn] != (uint32_t)j)
             continue;
         /* the one thread of the call that owns connection conn */
-        const uint32_t run = prefix_at(a.r0, a.r1, a.r2, j);
+        const uint32_t run = scan_at(a.runs, j);
         const uint32_t len = a.run_start[run + 1u] - (uint32_t)j;
         const uint32_t gen = gen_of(a, conn);
         a.conns[conn].next_pn = quic_tx_pn(a.conns[conn].next_pn, len);

@@ -426,6 +426,42 @@ def test_commit_then_open_again(engine, keyed, algo):
         rx.close()
 
 
+def test_commit_scratch_grows(engine, keyed):
+    """one receive object, one open_keyphase over 12 packets of 5 connections, then a commit with count = 2 and one with
+    count = 5: the minima and the scan levels grow between the two.  Connections 1 and 4 send next-generation packets: the first
+    commit finds connection 1's update and leaves entries 2 .. 4 alone, the second finds connection 4's and lowers first_pn
+    of 2 and 3.  Both lists and the table are the model's, applied in the same two steps; a third commit finds nothing left"""
+    states = [[c % 2, 100] for c in range(5)]
+    pk = [gen.short_packet(c, g, 120 + c, 8 + c % 2) for c, (g, _) in enumerate(states)]
+    pk += [gen.short_packet(c, states[c][0] + 1, 130 + c, 8) for c in (4, 1)]
+    pk += [gen.short_packet(c, g, 95 - c, 9) for c, (g, _) in enumerate(states)]  # reordered: below first_pn
+    case = gen.Case("aes128", states, 6, pk, gen.NCONN)
+    assert len(pk) == 12 and all(case.must_open(p) for p in pk)
+    keys = keyed(case)
+    buf, pkts, pkt_total, out_total = lay_out(case)
+    conns, res, pns, gens = gen.commit_inputs(case)
+    head = [list(s) for s in states[:2]]
+    first_upd = model.commit(head, conns, res, pns, gens)
+    after_first = head + [list(s) for s in states[2:]]
+    want = [list(s) for s in after_first]
+    second_upd = model.commit(want, conns, res, pns, gens)
+    assert (first_upd, second_upd) == ([1], [4]) and after_first[1] == [2, 131] and want[2:] == [[0, 93], [1, 92], [1, 134]]
+    rx = ptls_hip.QuicRx(engine, 0, len(pkts))
+    try:
+        load(rx, pkts)
+        d_phase = dev(phase_table(states).view(np.uint8))
+        o = Opened(rx, keys, d_phase, case.count, case.stride, dev(buf), pkt_total, out_total)
+        assert check(o, keys, states, case.stride, buf, pkts, range(len(pkts)), out_total) == res
+        assert (o.pns, o.gens) == (pns, gens)
+        assert commit(rx, o, d_phase, 2) == (first_upd, after_first)
+        assert commit(rx, o, d_phase, 5) == (second_upd, want)
+        again = [list(s) for s in want]
+        assert model.commit(again, conns, res, pns, gens) == [] and commit(rx, o, d_phase, 5) == ([], again)
+    finally:
+        torch.cuda.synchronize()
+        rx.close()
+
+
 def test_commit_groupings_of_bulk_traffic(engine, keyed):
     """1 500 packets of four connections in buffer order, laid out so that the mark pass folds a lane's successive packets,
     flushes when the place changes, reduces waves that hold one place (with the lowest packet number in lanes 37 and 13 of

@@ -134,9 +134,9 @@ def onekey(engine):
 
 class Synthetic:
     """a Call's packets as real packets in a receive object, opened: d_sel as the open call left it, d_result and d_pn_out
-    overwritten with the call's values"""
+    overwritten with the call's values.  rx: an existing receive object to load them into (the caller closes it)"""
 
-    def __init__(self, engine, keys, call, duds=True):
+    def __init__(self, engine, keys, call, duds=True, rx=None):
         self.call, self.m = call, len(call.packets)
         entries = []
         for j in range(self.m):
@@ -154,7 +154,8 @@ class Synthetic:
         # (a dud carries a type of another space than the packet in front of it: a type read at the position shows)
         info["type"] = [call.packets[e][1] if e is not None else (model.INITIAL if call.packets[entries[k - 1]][1] != model.INITIAL
                                                                    else model.ONE_RTT) for k, e in enumerate(entries)]
-        self.rx = ptls_hip.QuicRx(engine, 0, n)
+        self.own_rx = rx is None
+        self.rx = ptls_hip.QuicRx(engine, 0, n) if rx is None else rx
         try:
             load(self.rx, pkts, info)
             cap = n + 8
@@ -187,7 +188,8 @@ class Synthetic:
 
     def close(self):
         torch.cuda.synchronize()
-        self.rx.close()
+        if self.own_rx:
+            self.rx.close()
 
 
 @pytest.fixture
@@ -218,6 +220,32 @@ def test_the_case_list(synthetic, onekey, algo, part):
     s.run(expected=None)
     again = s.run(spaces=st.spaces())
     assert NEW not in again.verdicts() and again.n == 0 and again.spaces() == st.spaces()
+
+
+def track_slots(m):
+    """positions of the candidate table of m selected packets (csrc/quic_track.h quic_track_slots): the power of two from 2 m, at least 2"""
+    size = 2
+    while size < 2 * m:
+        size *= 2
+    return size
+
+
+def test_the_candidate_table_grows(engine, synthetic, onekey):
+    """one receive object: 3 packets of 2 connections loaded, opened and tracked, then 200 packets of 5 connections.  Between
+    the calls the candidate table grows (8 positions, then 512) and so do the per-space accumulators and the scan levels
+    (count 2, then 5): verdicts, the whole state table, the expected-pn table and the touched list are the model's both times,
+    so the regrown accumulators were zero and the regrown table held no candidate of the first call"""
+    small, large = gen.distinct_call(3, count=2), gen.distinct_call(200, count=5)
+    assert (track_slots(3), track_slots(200)) == (8, 512) and large.count > small.count
+    rx = ptls_hip.QuicRx(engine, 0, 256)
+    try:
+        a = synthetic(onekey("aes128"), small, rx=rx).run()
+        assert a.verdicts() == [NEW] * 3 and a.touched() == [0, 1]
+        b = synthetic(onekey("aes128"), large, rx=rx).run()
+        assert b.verdicts() == [NEW] * 200 and b.touched() == [0, 1, 2, 3, 4]
+    finally:
+        torch.cuda.synchronize()
+        rx.close()
 
 
 def test_order(synthetic, onekey):
