@@ -21,7 +21,8 @@
  *                      (kernels: quic_rx_kernel.hip; the select rule and the sums' terms shared with the CPU check: quic_rx.h),
  *                      and on it the key chosen by Key Phase bit and the commit of key updates (kernels:
  *                      quic_phase_kernel.hip; the rule shared with the CPU check: quic_phase.h), and the received packet
- *                      numbers tracked behind an open call (kernels: quic_track_kernel.hip; the rule: quic_track.h)
+ *                      numbers tracked behind an open call (kernels: quic_track_kernel.hip; the rule: quic_track.h), and
+ *                      the ACK frames and send requests written from them (kernels: quic_ack_kernel.hip; the rule: quic_ack.h)
  *   quic_tx.cpp        the QUIC send object: requests in device memory numbered, given headers and a key generation from a
  *                      per-connection state table on the device, compacted, planned and sealed there (kernels:
  *                      quic_tx_kernel.hip; the rule shared with the CPU check: quic_tx.h)

@@ -313,6 +313,32 @@ int launch_quic_track_verdict(const QuicTrackArgs &a, uint32_t m, unsigned grid,
  * the flags: each such space moved on by quic_track_apply, its expected_pn stored, acc reset, and c listed at its position */
 int launch_quic_track_apply(const QuicTrackArgs &a, int place, unsigned grid, void *stream);
 
+/* ---- ACK frames written from the tracked packet numbers (quic_ack_kernel.hip; the rule shared with the host and the CPU
+ * check: quic_ack.h) ---- */
+
+struct QuicAckArgs {
+    const ptls_hip_quic_pnspace_t *spaces; /* 3 x count entries: read only */
+    uint32_t count;
+    uint32_t space;
+    const uint32_t *list; /* n connections */
+    uint32_t n;
+    uint32_t max_ranges;
+    uint64_t ack_delay;
+    ScanRef lens;         /* over the frame lengths (0: no frame) */
+    ScanRef flags;        /* over the 0 / 1 "has a frame" flags */
+    uint64_t *sums;       /* [0] the frames' bytes, [1] their number: stored by the thread of the last list entry */
+    uint8_t *frames;
+    uint64_t in_off, pkt_base, pkt_stride;
+    uint32_t *status, *frame_off, *frame_len; /* the caller's three output arrays */
+    ptls_hip_quic_txreq_t *reqs;
+};
+
+/* one thread per list entry: the frame length into lens.l0, the flag into flags.l0 */
+int launch_quic_ack_size(const QuicAckArgs &a, unsigned grid, void *stream);
+/* after the scans over both: status, frame_off and frame_len of every entry, an ACK_OK entry's frame at its offset and its
+ * request at its compacted position, and the two sums (the last entry's prefixes plus its own terms) */
+int launch_quic_ack_write(const QuicAckArgs &a, unsigned grid, void *stream);
+
 /* quic_slice_kernel.hip, behind launch_quic_unprotect on a copy-transport slice: 8 bytes per packet at packed + 8 t = the
  * count of unprotected header bytes (0 with PTLS_HIP_QUIC_UNPROTECTED, else 1 + pn_len), the first byte, the packet-number
  * bytes, read from the packets at pkt */

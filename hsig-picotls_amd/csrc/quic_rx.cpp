@@ -9,6 +9,8 @@
  * quic_phase.h's, the kernels quic_phase_kernel.hip's.
  * And the received packet numbers tracked behind an open call (2k): the rule is quic_track.h's, the kernels
  * quic_track_kernel.hip's.
+ * And the ACK frames and send requests written from the tracked state (2m): the rule is quic_ack.h's, the
+ * kernels quic_ack_kernel.hip's.
  */
 #include <algorithm>
 #include <cstdio>
@@ -17,13 +19,14 @@
 #include "host.h"
 
 #define GF128_FN static inline
+#include "quic_ack.h"
 #include "quic_rx.h"
 #include "quic_track.h"
 
 namespace {
 
 thread_local bool g_timing = false;
-thread_local float g_select_ms = 0, g_plan_ms = 0, g_header_ms = 0, g_commit_ms = 0, g_track_ms = 0;
+thread_local float g_select_ms = 0, g_plan_ms = 0, g_header_ms = 0, g_commit_ms = 0, g_track_ms = 0, g_ack_ms = 0;
 
 } // namespace
 
@@ -31,7 +34,7 @@ struct st_ptls_hip_quic_rx_t {
     ptls_hip_engine_t *eng;
     size_t max_dgrams, cap;
     /* every d_ array below comes from here (rx_free: sc.release()); the timing events: select 0-1, sort 2-3, header kernel
-     * 4-5, commit 6-7, track 8-9 */
+     * 4-5, commit 6-7, track 8-9, ack 10-11 */
     DeviceScratch sc;
     size_t n = 0;          /* entries loaded */
     bool has_info = false; /* ... with info records */
@@ -61,10 +64,14 @@ struct st_ptls_hip_quic_rx_t {
     uint64_t *d_tk_acc = nullptr;
     uint32_t *d_tk_levels = nullptr, *d_tk_table = nullptr;
     size_t tk_cap = 0, tk_slots = 0;
+    /* the ack call's scratch, one array (ak_cap list entries): the scan levels over the frame lengths, those over the "has a
+     * frame" flags, and the two sums */
+    uint32_t *d_ak_levels = nullptr;
+    size_t ak_cap = 0;
     bool opened = false; /* an open call has run since the entries were loaded: d_packed holds its open_m selected packets */
     size_t open_m = 0;
 
-    st_ptls_hip_quic_rx_t(ptls_hip_engine_t *e, size_t dgrams, size_t c) : eng(e), max_dgrams(dgrams), cap(c), sc(e, "quic_rx", 10) {}
+    st_ptls_hip_quic_rx_t(ptls_hip_engine_t *e, size_t dgrams, size_t c) : eng(e), max_dgrams(dgrams), cap(c), sc(e, "quic_rx", 12) {}
     int ensure_entries()
     {
         if (int e = sc.ensure(&d_pkts, cap * sizeof(ptls_hip_quic_packet_t)))
@@ -541,5 +548,93 @@ extern "C" int ptls_hip_quic_rx_track(ptls_hip_quic_rx_t *rx, const ptls_hip_qui
     if (g_timing)
         g_track_ms = rx->sc.ev.between(8, 9);
     *n_touched = total;
+    return 0;
+}
+
+extern "C" void ptls_hip_quic_rx_ack_timing(float *ack_ms)
+{
+    if (ack_ms != nullptr)
+        *ack_ms = g_ack_ms;
+}
+
+extern "C" int ptls_hip_quic_rx_ack(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_rx_ack_t *pr, const uint32_t *d_list, size_t n,
+                                    ptls_hip_quic_rx_ack_report_t *report, void *stream)
+{
+    const char *who = "quic_rx_ack";
+    constexpr uint64_t MAX = PTLS_HIP_QUIC_ACK_MAX;
+    if (rx == nullptr || pr == nullptr || report == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null receive object, parameters or report", who);
+    if (pr->d_spaces == nullptr || pr->d_status == nullptr || pr->d_frame_off == nullptr || pr->d_frame_len == nullptr ||
+        pr->d_reqs == nullptr)
+        return fail(PTLS_HIP_EINVAL, "%s: null state, status, frame-offset, frame-length or request array", who);
+    if (n != 0 && (d_list == nullptr || pr->d_frames == nullptr))
+        return fail(PTLS_HIP_EINVAL, "%s: null list or frame buffer", who);
+    if (pr->count == 0 || pr->count > 0xffffffffu)
+        return fail(PTLS_HIP_EINVAL, "%s: a connection count of %zu is outside 1 .. 2^32 - 1", who, pr->count);
+    if (pr->space > 2)
+        return fail(PTLS_HIP_EINVAL, "%s: packet-number space %u is above 2", who, pr->space);
+    if (pr->ack_delay >= ptls_hip::QAK_VARINT_END)
+        return fail(PTLS_HIP_EINVAL, "%s: an ack_delay of %llu is not below 2^62", who, (unsigned long long)pr->ack_delay);
+    if (n > 0xffffffffu / MAX)
+        return fail(PTLS_HIP_EINVAL, "%s: %zu list entries: 81 bytes each do not fit the 32-bit scan levels", who, n);
+    if (pr->frames_len < MAX * n)
+        return fail(PTLS_HIP_EINVAL, "%s: a frame buffer of %zu bytes is below 81 for each of the %zu list entries", who, pr->frames_len, n);
+    if (pr->in_off > UINT64_MAX - MAX * n)
+        return fail(PTLS_HIP_EINVAL, "%s: in_off plus 81 bytes for each of the %zu list entries wraps 2^64", who, n);
+    if (pr->pkt_stride != 0 && n > (UINT64_MAX - pr->pkt_base) / pr->pkt_stride)
+        return fail(PTLS_HIP_EINVAL, "%s: pkt_base plus %zu packets of stride %llu wraps 2^64", who, n, (unsigned long long)pr->pkt_stride);
+    report->n_frames = 0;
+    report->bytes = 0;
+    if (n == 0)
+        return 0;
+
+    ptls_hip_engine_t *eng = rx->eng;
+    DeviceGuard g(eng->device);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    /* (the words of n entries' levels grow with n: two sets of them and the sums fit what the capacity allocated) */
+    if (int e = rx->sc.grow(&rx->ak_cap, n, s, {{&rx->d_ak_levels, (2 * scan_levels(nullptr, n).words + 4) * sizeof(uint32_t)}}))
+        return e;
+    const size_t words = scan_levels(nullptr, n).words; /* a multiple of 4: the sums behind both are 16-byte aligned */
+    const ScanLevels Ll = scan_levels(rx->d_ak_levels, n), Lf = scan_levels(rx->d_ak_levels + words, n);
+    uint64_t *d_sums = reinterpret_cast<uint64_t *>(rx->d_ak_levels + 2 * words);
+    QuicAckArgs a{};
+    a.spaces = pr->d_spaces;
+    a.count = (uint32_t)pr->count;
+    a.space = pr->space;
+    a.list = d_list;
+    a.n = (uint32_t)n;
+    a.max_ranges = pr->max_ranges;
+    a.ack_delay = pr->ack_delay;
+    a.lens = Ll.ref();
+    a.flags = Lf.ref();
+    a.sums = d_sums;
+    a.frames = static_cast<uint8_t *>(pr->d_frames);
+    a.in_off = pr->in_off;
+    a.pkt_base = pr->pkt_base;
+    a.pkt_stride = pr->pkt_stride;
+    a.status = pr->d_status;
+    a.frame_off = pr->d_frame_off;
+    a.frame_len = pr->d_frame_len;
+    a.reqs = pr->d_reqs;
+    const unsigned grid = quic_scan_grid((n + 255) / 256, eng->ncu);
+    rx->sc.ev.mark(g_timing, 10, s);
+    int e = launch_quic_ack_size(a, grid, stream);
+    if (e == 0)
+        e = launch_scan_levels(Ll, eng->ncu, stream);
+    if (e == 0)
+        e = launch_scan_levels(Lf, eng->ncu, stream);
+    if (e == 0)
+        e = launch_quic_ack_write(a, grid, stream);
+    if (e != 0)
+        return fail(PTLS_HIP_ELAUNCH, "%s: kernel launch failed: %s", who, hipGetErrorString((hipError_t)e));
+    rx->sc.uses.note(stream);
+    rx->sc.ev.mark(g_timing, 11, s);
+    uint64_t sums[2] = {};
+    HIP_TRY(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s), PTLS_HIP_ENODEV);
+    HIP_TRY(hipStreamSynchronize(s), PTLS_HIP_ENODEV);
+    if (g_timing)
+        g_ack_ms = rx->sc.ev.between(10, 11);
+    report->bytes = sums[0];
+    report->n_frames = sums[1];
     return 0;
 }

@@ -18,7 +18,7 @@ struct ScanLevels {
 /* the timing events of one owner (`count` of them, at most MAX), each created with its first mark; between() is 0 unless
  * both were marked.  No heap memory: the parse call builds one per call */
 struct TimingEvents {
-    static constexpr int MAX = 10;
+    static constexpr int MAX = 12;
     hipEvent_t ev[MAX] = {};
     const int count;
     explicit TimingEvents(int n) : count(n) {}
@@ -48,7 +48,7 @@ struct DeviceScratch {
     const char *prefix; /* of the out-of-memory message: "quic_rx", "quic_tx" */
     Uses uses;          /* the launches that read or write the arrays */
     TimingEvents ev;
-    static constexpr size_t MAX_ARRAYS = 24; /* (the receive object has 19; one more than this is refused, not lost) */
+    static constexpr size_t MAX_ARRAYS = 24; /* (the receive object has 20; one more than this is refused, not lost) */
     void *owned[MAX_ARRAYS] = {};
     size_t n_owned = 0;
 

@@ -56,6 +56,9 @@ QUIC_NO_GEN = 0xFFFFFFFF
 QUIC_PNSPACE_DTYPE = np.dtype([("next", "<u8"), ("window", "<u8")])
 assert QUIC_PNSPACE_DTYPE.itemsize == 16
 QUIC_PN_NONE, QUIC_PN_NEW, QUIC_PN_DUPLICATE, QUIC_PN_TOO_OLD = range(4)
+# the ACK frames written from that state (QuicRx.ack): the status of a list entry, and the longest frame
+QUIC_ACK_OK, QUIC_ACK_NO_CONN, QUIC_ACK_EMPTY, QUIC_ACK_STATE = range(4)
+QUIC_ACK_MAX = 81
 # ptls_hip_quic_txconn_t / ptls_hip_quic_txreq_t: a connection's send state and one send request (the send object, QuicTx)
 QUIC_TXCONN_DTYPE = np.dtype([("next_pn", "<u8"), ("largest_acked", "<u8"), ("gen", "<u4"), ("dcid_len", "u1"), ("flags", "u1"),
                               ("reserved", "u1", (2,)), ("dcid", "u1", (20,)), ("reserved2", "u1", (4,))])
@@ -146,6 +149,9 @@ SIGNATURES = {
     "ptls_hip_quic_rx_track": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_sz), _vp]),
     # diagnostic only (tools/bench_quic_track.py): HIP-event time of the last track call's launches
     "ptls_hip_quic_rx_track_timing": (None, [ctypes.POINTER(ctypes.c_float)]),
+    "ptls_hip_quic_rx_ack": (_i, [_vp, _vp, _vp, _sz, _vp, _vp]),
+    # diagnostic only (tools/bench_quic_ack.py): HIP-event time of the last ack call's launches
+    "ptls_hip_quic_rx_ack_timing": (None, [ctypes.POINTER(ctypes.c_float)]),
     "ptls_hip_quic_tx_new": (_vp, [_vp, _sz]),
     "ptls_hip_quic_tx_free": (None, [_vp]),
     "ptls_hip_quic_tx_seal": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
@@ -605,6 +611,19 @@ class QuicRxTrack(ctypes.Structure):
                 ("expected_count", ctypes.c_size_t), ("d_verdict", ctypes.c_void_p), ("d_touched", ctypes.c_void_p)]
 
 
+class QuicRxAck(ctypes.Structure):
+    """ptls_hip_quic_rx_ack_t"""
+    _fields_ = [("d_spaces", ctypes.c_void_p), ("count", ctypes.c_size_t), ("space", ctypes.c_uint32), ("max_ranges", ctypes.c_uint32),
+                ("ack_delay", ctypes.c_uint64), ("d_frames", ctypes.c_void_p), ("frames_len", ctypes.c_size_t), ("in_off", ctypes.c_uint64),
+                ("pkt_base", ctypes.c_uint64), ("pkt_stride", ctypes.c_uint64), ("d_status", ctypes.c_void_p),
+                ("d_frame_off", ctypes.c_void_p), ("d_frame_len", ctypes.c_void_p), ("d_reqs", ctypes.c_void_p)]
+
+
+class QuicRxAckReport(ctypes.Structure):
+    """ptls_hip_quic_rx_ack_report_t"""
+    _fields_ = [("n_frames", ctypes.c_uint64), ("bytes", ctypes.c_uint64)]
+
+
 class QuicRx:
     """the receive object (ptls_hip_quic_rx_*): parsed entries stay on the device; open() selects, packs, plans and opens
     them there.  Calls on one QuicRx must be ordered (same stream)."""
@@ -706,6 +725,19 @@ class QuicRx:
         _check(lib().ptls_hip_quic_rx_track(self.ptr, ctypes.addressof(tr), _ptr(d_sel), _ptr(d_result), _ptr(d_pn_out),
                                             ctypes.byref(n), _stream(stream)), "quic_rx_track")
         return n.value
+
+    def ack(self, d_spaces, count, space, d_list, n, d_frames, frames_len, d_status, d_frame_off, d_frame_len, d_reqs, ack_delay=0,
+            max_ranges=31, in_off=0, pkt_base=0, pkt_stride=0, stream=None):
+        """one ACK frame (RFC 9000 §19.3, type 0x02) per entry of d_list (device, uint32 connections; typically track()'s
+        d_touched) from d_spaces' entries of `space`, packed into d_frames; d_status[j] = QUIC_ACK_*, d_frame_off[j] and
+        d_frame_len[j] as include/ptls_hip.h 2m defines them; d_reqs (device, QUIC_TXREQ_DTYPE, room for n) receives one request
+        per frame, as QuicTx.seal takes them; returns the QuicRxAckReport (n_frames, bytes)"""
+        rep = QuicRxAckReport()
+        pr = QuicRxAck(_ptr(d_spaces), count, space, max_ranges, ack_delay, _ptr(d_frames), frames_len, in_off, pkt_base, pkt_stride,
+                       _ptr(d_status), _ptr(d_frame_off), _ptr(d_frame_len), _ptr(d_reqs))
+        _check(lib().ptls_hip_quic_rx_ack(self.ptr, ctypes.addressof(pr), _ptr(d_list), n, ctypes.addressof(rep), _stream(stream)),
+               "quic_rx_ack")
+        return rep
 
     def close(self):
         if self.ptr:

@@ -925,8 +925,9 @@ typedef struct st_ptls_hip_quic_pnspace_t {
  *   n_touched; count == 0 or above 2^32 - 1; d_expected_pn == NULL with expected_count != 0; no open on the object since its
  *   entries were loaded; entries loaded without info records (rx_set_packets with d_info == NULL).
  *   The call's scratch belongs to the object: allocated with the first use, grown when a call needs more, released by rx_free.
- * Out of scope: windows wider than 64; ACK frames and ACK ranges (the host reads the state entries of the listed
- * connections); the batches of 2e, the pipelines of 2g and the node API; discarding packet-number spaces; ECN counts. */
+ * ACK frames and ACK ranges for the listed connections: 2m, from d_touched as it is.
+ * Out of scope: windows wider than 64; the batches of 2e, the pipelines of 2g and the node API; discarding packet-number
+ * spaces; ECN counts; knowing whether a packet was ack-eliciting (a frame walk over the opened payloads). */
 typedef struct st_ptls_hip_quic_rx_track_t {
     ptls_hip_quic_pnspace_t *d_spaces; /* device: 3 * count entries */
     size_t count;                      /* connections */
@@ -1023,7 +1024,9 @@ typedef struct st_ptls_hip_quic_txreq_t { /* 24 bytes */
  *   pointer, NULL when none), and their number.
  * tx_timing: diagnostic (tools/bench_quic_tx.py), as rx_timing: with it enabled on the calling thread, the HIP-event times of
  *   the last tx_seal's launches in front of the record kernel (numbering, select, build, state) and of its sort launches.
- * Out of scope: long headers; coalescing; padding; frame building; in-place payloads (d_in inside d_pkt); the host pipelines
+ * ACK frames and their requests come from 2m (rx_ack writes d_reqs on the device).
+ * Out of scope: long headers; coalescing; padding; building other frames, and bundling them with an ACK frame; reading
+ * received ACK frames into largest_acked; in-place payloads (d_in inside d_pkt); the host pipelines
  * (2g) and the node API (2d); the AEAD usage limits of RFC 9001 §6.6; the host plan (key-run chunks for the AES batch
  * kernel). */
 typedef struct st_ptls_hip_quic_tx_t ptls_hip_quic_tx_t;
@@ -1052,6 +1055,81 @@ int ptls_hip_quic_tx_seal(ptls_hip_quic_tx_t *tx, ptls_hip_keyset_t *ks, ptls_hi
 const ptls_hip_quic_packet_t *ptls_hip_quic_tx_packets(ptls_hip_quic_tx_t *tx);
 size_t ptls_hip_quic_tx_count(ptls_hip_quic_tx_t *tx);
 void ptls_hip_quic_tx_timing(int enable, float *front_ms, float *sort_ms);
+
+/* ------------------------------------------------------------------------------------------ *
+ * 2m. ACK frames written on the device from the tracked packet numbers, with the send requests  *
+ *     that carry them (RFC 9000 §13.2, §16, §19.3)                                               *
+ * ------------------------------------------------------------------------------------------ */
+
+/* rx_track (2k) leaves "which packet numbers have we accepted" in a device table and lists the connections that received
+ * something new; tx_seal (2l) starts at "connection c, payload here, packet there".  rx_ack is the step between: for a
+ * DEVICE list of connections it writes one ACK frame each from the state entries, packed back to back, and one send request
+ * per frame.  d_touched -> rx_ack -> tx_seal needs no host step beyond reading two sums.
+ *
+ * The frame is RFC 9000 §19.3's, type 0x02 (no ECN counts), a pure function of one entry (next, window) of space `space`:
+ *   The accepted set is packet number next - 1 - k for every set bit k of window with k < min(64, next); bits at k >= next are
+ *   ignored, not an error.  A run is a maximal stretch of consecutive set bits, taken from bit 0 upwards; run 0 starts at bit 0.
+ *   The fields, in order: Largest Acknowledged = next - 1; ACK Delay = ack_delay as given (the caller has applied its
+ *   ack_delay_exponent); ACK Range Count r = min(runs behind run 0, max_ranges); First ACK Range = len(run 0) - 1; for
+ *   i = 1 .. r: Gap = (clear bits between run i - 1 and run i) - 1, ACK Range Length = len(run i) - 1.  Older runs beyond
+ *   max_ranges are dropped (a 64-bit window has at most 31 behind run 0; max_ranges above 31 behaves like 31).
+ *   Varints are of minimal length; every range field is below 64 and takes one byte, so the frame has
+ *   1 + vl(next - 1) + vl(ack_delay) + 2 + 2 r bytes: 5 .. PTLS_HIP_QUIC_ACK_MAX.
+ * The status of list entry j with conn = d_list[j], in this precedence: ACK_NO_CONN for conn >= count; ACK_EMPTY for
+ * next == 0; ACK_STATE for next > 2^62 or bit 0 of window clear (the table is the caller's: a corrupt entry must not produce a
+ * frame that acknowledges nothing, or a number that cannot exist); else ACK_OK.  Only ACK_OK entries get a frame.
+ *
+ * After the call exactly n elements of d_status, d_frame_off and d_frame_len are written: d_frame_len[j] = the frame length,
+ * 0 unless ACK_OK; d_frame_off[j] = the sum of d_frame_len over the entries before j, for every j.  The frames lie back to back
+ * in list order at d_frames + d_frame_off[j]; report->bytes is their sum and exactly that many bytes of d_frames change.  (They
+ * are packed, not strided: a typical frame has 5 to 13 bytes against the 81 of the worst case.)  The j'-th ACK_OK entry in list
+ * order writes d_reqs[j'] = {data_off = in_off + d_frame_off[j], pkt_off = pkt_base + j' * pkt_stride, conn, len =
+ * d_frame_len[j]}; exactly report->n_frames requests are written.  tx_seal takes them as they are, with d_frames lying at
+ * in_off inside its d_in: a frame has at least 5 bytes, which meets its sample rule, and whether pkt_stride holds a packet stays
+ * with its TX_RANGE.  The state table is not written.  Duplicates in the list are legal, each gets a frame.  The outcome does
+ * not depend on the order in which the entries are looked at.  One stream synchronisation, to read the two sums.  n == 0:
+ * 0 with both sums 0 and nothing written.
+ * The object is only the owner of the scratch and the engine handle, as for rx_track: no loaded entries and no open call are
+ * needed.  The scratch is allocated with the first use and grown when a call has more entries: a steady-state call allocates
+ * nothing.  Calls on one receive object must be ordered by the caller (same stream).
+ * PTLS_HIP_EINVAL, nothing launched and nothing written: a null object, params, report, d_spaces, d_status, d_frame_off,
+ * d_frame_len or d_reqs; n != 0 with a null d_list or d_frames; count == 0 or above 2^32 - 1; space > 2; ack_delay >= 2^62;
+ * 81 n > 2^32 - 1 (the scan levels are 32-bit); frames_len < 81 n (so that no refusal depends on the data); in_off + 81 n or
+ * pkt_base + n * pkt_stride wrapping 2^64.
+ * Policy: the call acknowledges every listed connection.  Not answering ACK-only packets with ACK-only packets (RFC 9000
+ * §13.2.1) stays the host's duty, through the list it passes.
+ * Out of scope: ECN counts (type 0x03); a delay per connection; windows wider than 64; other frames bundled into the same
+ * packet; reading received ACK frames into txconn.largest_acked, and knowing whether a packet was ack-eliciting (both need a
+ * frame walk over the opened payloads). */
+#define PTLS_HIP_QUIC_ACK_MAX 81
+#define PTLS_HIP_QUIC_ACK_OK 0u
+#define PTLS_HIP_QUIC_ACK_NO_CONN 1u /* the connection lies outside the state table */
+#define PTLS_HIP_QUIC_ACK_EMPTY 2u   /* nothing accepted yet in that space */
+#define PTLS_HIP_QUIC_ACK_STATE 3u   /* not a state rx_track leaves: next above 2^62, or the largest number not accepted */
+typedef struct st_ptls_hip_quic_rx_ack_t { /* 104 bytes */
+    const ptls_hip_quic_pnspace_t *d_spaces; /* device: 2k's table, 3 * count entries */
+    size_t count;                            /* connections */
+    uint32_t space;                          /* 0 Initial, 1 Handshake, 2 0-RTT and 1-RTT */
+    uint32_t max_ranges;                     /* ACK ranges to keep behind the first; above 31: 31 */
+    uint64_t ack_delay;                      /* the ACK Delay field, below 2^62 */
+    void *d_frames;                          /* device: the frames, packed */
+    size_t frames_len;                       /* its bytes: at least 81 n */
+    uint64_t in_off;                         /* where d_frames lies inside the d_in that tx_seal will get */
+    uint64_t pkt_base, pkt_stride;           /* request j' sends its packet to pkt_base + j' * pkt_stride */
+    uint32_t *d_status;                      /* device: one PTLS_HIP_QUIC_ACK_* per list entry */
+    uint32_t *d_frame_off;                   /* device: one per list entry */
+    uint32_t *d_frame_len;                   /* device: one per list entry */
+    ptls_hip_quic_txreq_t *d_reqs;           /* device, room for n */
+} ptls_hip_quic_rx_ack_t;
+typedef struct st_ptls_hip_quic_rx_ack_report_t {
+    uint64_t n_frames;
+    uint64_t bytes;
+} ptls_hip_quic_rx_ack_report_t;
+int ptls_hip_quic_rx_ack(ptls_hip_quic_rx_t *rx, const ptls_hip_quic_rx_ack_t *params, const uint32_t *d_list, size_t n,
+                         ptls_hip_quic_rx_ack_report_t *report, void *stream);
+/* Diagnostic (tools/bench_quic_ack.py): with ptls_hip_quic_rx_timing enabled on the calling thread, the HIP-event time of the
+ * last rx_ack's launches (the pointer may be NULL). */
+void ptls_hip_quic_rx_ack_timing(float *ack_ms);
 
 /* ------------------------------------------------------------------------------------------ *
  * 3. synthetic workload (bench / tests): the payload of descriptor i is the splitmix64 stream     *
